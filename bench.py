@@ -2,10 +2,16 @@
 """Benchmark: Mrays/s of the MI355X path integrator on the BASELINE.json config
 (CornellBox-Original, 1920x1080, 512 spp, path + NEE + MIS), with the image
 tiles sharded over N GPUs (one process per GPU, RCCL gather of the tile
-radiance to rank 0 over xGMI), plus the roofline of the path megakernel and
-the CPU baseline (the fp64 C restatement, oracle/, timed on this host's cores).
+radiance to rank 0 over xGMI), plus the roofline of the path megakernel (from
+the recorded counter profiles; no run of its own).
 
-The same JSON line carries the north-star run (BASELINE.json north_star, SURVEY
+A plain run does only what the headline figure needs: scene build and upload,
+W warm-up frames, K timed frames, the result line.  --dump-outputs DIR also
+writes the film of the last timed frame as DIR/film.npy.  Everything else is
+behind --full: the CPU baseline and the RMSE against it (the fp64 C
+restatement, oracle/, timed on this host's cores) and the blocks below.
+
+With --full the same JSON line carries the north-star run (BASELINE.json north_star, SURVEY
 §8(d) C4): the 1,005,858-triangle tessellated Cornell box at 1920x1080 / 512
 spp, sharded the same way, timed the same way, with its own RMSE against the
 oracle and its own roofline ("north_star": {...}).  It also carries BASELINE.json's
@@ -13,7 +19,7 @@ configs[2] and [4] as blocks "c3" (veach_mi 1080p 1024 spp, the fp64 list-world
 kernel) and "c5" (PSS-MLT on CornellBox 1080p, 512 mutations per pixel, 2^18
 chains), each timed the same way (3 frames after 1 warm-up) with its own RMSE
 against the oracle (C5: path-exact on a chain shard of the config), roofline
-and CPU figure, so the driver's default run measures four of the five configs
+and CPU figure, so the default --full run measures four of the five configs
 (C1 is the reference's own CPU plumbing case).
 
 One "step" = one full frame: every rank renders its tiles (tile t -> rank
@@ -22,6 +28,7 @@ which scatters them into the film.  Scene build and upload happen before the
 timed region.
 
     python bench.py [--gpus N --steps K --warmup W] [--scene cornell|cornell_1m|veach|sphere]
+                    [--dump-outputs DIR] [--full]
 
 Prints ONE JSON line on rank 0.
 """
@@ -754,6 +761,25 @@ def block_common(r, world):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, film, nx, ny, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the film the timed path returned from its last step, as
+    outdir/film.npy (float32, ny x nx x 3).  A film over `max_bytes` is written
+    as a fixed, seeded sample of its pixels instead: film.npy holds their rows
+    (n x 3) and film_pixels.npy their indices y * nx + x (float64, exact), the
+    same pixels on every run of the same frame size."""
+    os.makedirs(outdir, exist_ok=True)
+    img = np.ascontiguousarray(np.asarray(film, np.float32).reshape(ny, nx, 3))
+    if img.nbytes > max_bytes:
+        n = max(1, int(max_bytes // (3 * 4 + 8)))
+        pix = np.sort(np.random.default_rng(0x5EED).choice(nx * ny, size=n, replace=False))
+        np.save(os.path.join(outdir, "film_pixels.npy"), pix.astype(np.float64))
+        img = np.ascontiguousarray(img.reshape(-1, 3)[pix])
+    np.save(os.path.join(outdir, "film.npy"), img)
+
+
 def first_ray_estimate(cpu_mrays):
     """cpu_baseline / (the port's 1-thread Mrays/s on C1 over first_ray's), or None."""
     rec = None
@@ -796,13 +822,19 @@ def main():
     ap.add_argument("--cpu-pixels", type=int, default=0, help="pixels in the CPU-baseline sample (0: calibrated)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-baseline duration when calibrated")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every CPU this process may use (host_cpus)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline and the "
+                         "RMSE against the oracle, and (default config) the north-star, C3 and C5 blocks")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the film of the last timed step to DIR/film.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the oracle's CPU work")
     ap.add_argument("--north-star", default="auto", choices=["auto", "on", "off"],
-                    help="auto: with the default config (cornell, path) also run cornell_1m 1080p/512spp")
+                    help="with --full; auto: with the default config (cornell, path) also run cornell_1m "
+                         "1080p/512spp")
     ap.add_argument("--ns-steps", type=int, default=3, help="timed frames of the north-star run")
     ap.add_argument("--ns-pixels", type=int, default=32768, help="oracle pixel sample for the north-star RMSE")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="auto: with the default config also run BASELINE's C3 (veach_mi 1080p 1024 spp) and C5 "
+                    help="with --full; auto: with the default config also run BASELINE's C3 (veach_mi 1080p 1024 spp) and C5 "
                          "(PSS-MLT on CornellBox 1080p, 512 mutations/pixel) as blocks \"c3\" and \"c5\"")
     ap.add_argument("--cfg-steps", type=int, default=3, help="timed frames of each configuration block")
     ap.add_argument("--cfg-cpu-seconds", type=float, default=10.0,
@@ -825,6 +857,11 @@ def main():
     ap.add_argument("--rmse-pixels-multi", type=int, default=32768,
                     help="N > 1: oracle pixel sample for rank 0's RMSE (no CPU timing at N > 1)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        if args.north_star == "on" or args.configs == "on":
+            ap.error("--north-star on / --configs on need --full")
+        args.no_cpu_baseline, args.north_star, args.configs = True, "off", "off"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the N ranks here, before anything touches the GPU
@@ -858,7 +895,7 @@ def main():
             with Heartbeat("C5 parity (oracle)"):
                 c5_cpu = cpu_baseline_mlt(R.ctx, c5, 512, args.chains, args.seed, threads, args.cfg_cpu_seconds)
 
-    beat = Heartbeat("oracle RMSE / CPU baseline") if rank == 0 else None
+    beat = Heartbeat("oracle RMSE / CPU baseline") if rank == 0 and args.full else None
     if beat is not None:
         beat.__enter__()
     if rank == 0:
@@ -1012,7 +1049,10 @@ def main():
             line["config"]["parallelism"] += " (gloo host-staged rehearsal)"
         if args.pfm:
             R.frt.write_pfm(args.pfm, film_np.reshape(ny, nx, 3))
-        beat.__exit__()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, film_np, nx, ny)
+        if beat is not None:
+            beat.__exit__()
         print(json.dumps(line), flush=True)
     R.ctx.close()
     if world > 1:

@@ -8,6 +8,7 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,3 +123,33 @@ def test_roofline_clock_fields():
     assert out["bound"] == "valu" and out["clock_ghz"] == round(pmc["clock_ghz"], 3)
     assert 1.9 < out["clock_ghz"] <= 2.4
     assert out["valu_issue_frac_at_clock"] == round(out["frac"] * bench.VALU_PEAK_CLOCK_GHZ / pmc["clock_ghz"], 4)
+
+
+def test_blocks_need_full():
+    """The north-star and configuration blocks are behind --full: asking for
+    one in a plain run is refused before anything starts."""
+    for opt in ("--north-star", "--configs"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt, "on"],
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 2 and p.stdout.strip() == "" and "--full" in p.stderr
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: the whole film as float32 while it fits the size limit;
+    above it the same seeded pixel sample every time, with its indices."""
+    rng = np.random.default_rng(1)
+    nx, ny = 37, 23
+    film = rng.random(nx * ny * 3, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), film, nx, ny)
+    assert os.listdir(tmp_path / "a") == ["film.npy"]
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and got.shape == (ny, nx, 3) and np.array_equal(got.reshape(-1), film)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), film, nx, ny, max_bytes=2000)
+    rows, pix = np.load(tmp_path / "b" / "film.npy"), np.load(tmp_path / "b" / "film_pixels.npy")
+    assert rows.dtype == np.float32 and pix.dtype == np.float64
+    assert rows.nbytes + pix.nbytes <= 2000 and len(rows) == len(pix) == 100
+    idx = pix.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < nx * ny
+    assert np.array_equal(rows, film.reshape(-1, 3)[idx])
+    assert np.array_equal(pix, np.load(tmp_path / "c" / "film_pixels.npy"))

@@ -4,7 +4,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/${TAG:-lines}; mkdir -p $O
-b() { name=$1; shift; timeout -k 10 300 python bench.py --steps 2 --warmup 1 --north-star off --cpu-seconds 3 "$@" > $O/$name.json 2> $O/$name.log; }
+b() { name=$1; shift; timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --north-star off --cpu-seconds 3 "$@" > $O/$name.json 2> $O/$name.log; }
 b veach --scene veach --spp 1024 \
  && b pssmlt --integrator pssmlt \
  && b ao --integrator ao \

@@ -26,7 +26,7 @@ pmc() {  # name, counters, bench args...
       python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --north-star off "$@" > $O/$n.json 2> $O/$n.log
 }
 if [ "${PART:-a}" = a ]; then
-  trace default 420 --steps ${STEPS:-5} --warmup 1 \
+  trace default 420 --full --steps ${STEPS:-5} --warmup 1 \
    && pmc sq_cornell "$SQ" && pmc fetch_cornell FETCH_SIZE && pmc write_cornell WRITE_SIZE \
    && pmc sq_1m "$SQ" --scene cornell_1m && pmc fetch_1m FETCH_SIZE --scene cornell_1m \
    && pmc write_1m WRITE_SIZE --scene cornell_1m && pmc tcc_1m "TCC_HIT TCC_MISS" --scene cornell_1m

@@ -10,7 +10,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -v -rA --timeout 300 --timeou
 rc=$?
 echo "pytest rc=$rc" > $O/rc.txt
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi   # 1 = test failures: still bench; anything else (fault, timeout) stops
-timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.log
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.log
 rc2=$?
 echo "bench rc=$rc2" >> $O/rc.txt
 exit $(( rc > rc2 ? rc : rc2 ))
