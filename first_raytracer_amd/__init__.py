@@ -182,7 +182,9 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_scene_build_bvh_sah", "frt_scene_build_bvh_gpu_algo",
            "frt_scene_view_get", "frt_scene_info", "frt_scene_destroy", "frt_write_tessellated_obj",
            "frt_write_pfm", "frt_film_accumulate", "frt_tonemap_u8", "frt_write_image", "frt_selftest_path_host",
-           "frt_selftest_mlt_paths_host")
+           "frt_selftest_mlt_paths_host",
+           "frt_set_env_image", "frt_scene_set_env_image", "frt_scene_env_image", "frt_read_hdr",
+           "frt_selftest_path_host_env")
 
 
 def lib():
@@ -245,6 +247,12 @@ def lib():
                                          ctypes.c_int, vp, ctypes.POINTER(Stats)]
     L.frt_selftest_mlt_paths_host.argtypes = [ctypes.POINTER(SceneView), ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
                                               ctypes.c_int, vp]
+    L.frt_set_env_image.argtypes = [vp, ctypes.POINTER(Image)]
+    L.frt_scene_set_env_image.argtypes = [vp, ctypes.c_int]
+    L.frt_scene_env_image.argtypes = [vp, ctypes.POINTER(Image)]
+    L.frt_read_hdr.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), vp]
+    L.frt_selftest_path_host_env.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp,
+                                             ctypes.c_int, ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
     _lib = L
     return L
 
@@ -273,6 +281,21 @@ class HostScene:
         (material.h:206-232; the reference scenes use black)."""
         self.env = tuple(float(x) for x in rgb)
 
+    def set_env_image(self, index):
+        """Image `index` of the scene (spec "images") is its environment map
+        (frt_scene_set_env_image); -1 or None = the constant colour again.
+        Context.upload() forwards it to the context."""
+        _check(lib().frt_scene_set_env_image(self.ptr, -1 if index is None else int(index)), "frt_scene_set_env_image")
+
+    def env_image(self):
+        """The scene's environment image as an Image (frt_scene_env_image; its
+        data belongs to the scene), or None."""
+        img = Image()
+        rc = lib().frt_scene_env_image(self.ptr, ctypes.byref(img))
+        if rc < 0:
+            _check(rc, "frt_scene_env_image")
+        return img if rc == 1 else None
+
     @classmethod
     def from_spec(cls, spec, aspect):
         """Build a scene the way main.cpp's scene functions do (frt_scene_new ...
@@ -283,7 +306,8 @@ class HostScene:
                         "where": "world" | "lights" | "both"}, ...],
            "camera": {"lookfrom", "lookat", "vup", "vfov", "aperture", "focus"},
            "world": "bvh" | "list", "env": (r, g, b) | None,
-           "images": [{"data": (ny, nx, 3) uint8 sRGB | float32}, ...]}
+           "images": [{"data": (ny, nx, 3) uint8 sRGB | float32}, ...],
+           "env_image": index into "images" (the environment map) | None}
         material: {"type": "lambertian" | "diffuse_light" | "modified_phong" |
                    "metal" | "dielectric" | "rough_conductor", "albedo", "emit",
                    "specular", "exponent", "ior", "alpha", "distribution":
@@ -323,6 +347,8 @@ class HostScene:
         if spec.get("env") is not None:
             e = dptr(spec["env"])
             _check(L.frt_scene_set_env(self.ptr, e[1]), "frt_scene_set_env")
+        if spec.get("env_image") is not None:
+            _check(L.frt_scene_set_env_image(self.ptr, int(spec["env_image"])), "frt_scene_set_env_image")
         _check(L.frt_scene_finish(self.ptr, {"bvh": 0, "list": 1}[spec.get("world", "bvh")]), "frt_scene_finish")
         self.info = HostSceneInfo()
         L.frt_scene_info(self.ptr, ctypes.byref(self.info))
@@ -397,8 +423,31 @@ class Context:
         _check(lib().frt_set_precision(self.ptr, int(precision)), "frt_set_precision", self.ptr)
 
     def upload(self, scene):
+        """frt_upload_scene.  A HostScene with an environment image
+        (HostScene.set_env_image / spec "env_image") also sets it on the context; one
+        without clears an image that an earlier upload() forwarded.  An image set
+        with Context.set_env_image stays until that call changes it."""
         view = scene.view() if isinstance(scene, HostScene) else scene
         _check(lib().frt_upload_scene(self.ptr, ctypes.byref(view)), "frt_upload_scene", self.ptr)
+        img = scene.env_image() if isinstance(scene, HostScene) else None
+        if img is not None:
+            _check(lib().frt_set_env_image(self.ptr, ctypes.byref(img)), "frt_set_env_image", self.ptr)
+            self._env_from_scene = True
+        elif isinstance(scene, HostScene) and getattr(self, "_env_from_scene", False):
+            _check(lib().frt_set_env_image(self.ptr, None), "frt_set_env_image", self.ptr)
+            self._env_from_scene = False
+
+    def set_env_image(self, image):
+        """The context's environment map (frt_set_env_image): a (ny, nx, 3)
+        uint8 (sRGB) or float32 array, copied to the device and kept across
+        upload(); None = the constant env colour of the uploaded scene."""
+        self._env_from_scene = False
+        if image is None:
+            _check(lib().frt_set_env_image(self.ptr, None), "frt_set_env_image", self.ptr)
+            return
+        a, fmt = image_array({"data": image})
+        desc = Image(a.shape[1], a.shape[0], fmt, 0, a.ctypes.data)
+        _check(lib().frt_set_env_image(self.ptr, ctypes.byref(desc)), "frt_set_env_image", self.ptr)
 
     def render(self, params, film=None):
         """Render into a full film (nx*ny*3 float32, y=0 bottom row).  Returns (film, stats)."""
@@ -472,15 +521,23 @@ def shard_slots(params):
     return out
 
 
-def selftest_path_host(scene, params, pixels):
+def selftest_path_host(scene, params, pixels, env_image=None):
     """Self-test hook: the megakernel's per-lane path code run on the host
-    (CPU unit tests of the device logic; never a render path)."""
+    (CPU unit tests of the device logic; never a render path).  env_image: a
+    (ny, nx, 3) uint8 / float32 environment map, read as a render reads it."""
     pixels = np.ascontiguousarray(pixels, dtype=np.int32)
     out = np.zeros((len(pixels), 3), np.float32)
     st = Stats()
     view = scene.view()
-    _check(lib().frt_selftest_path_host(ctypes.byref(view), ctypes.byref(params), pixels.ctypes.data, len(pixels),
-                                        out.ctypes.data, ctypes.byref(st)), "frt_selftest_path_host")
+    if env_image is None:
+        _check(lib().frt_selftest_path_host(ctypes.byref(view), ctypes.byref(params), pixels.ctypes.data, len(pixels),
+                                            out.ctypes.data, ctypes.byref(st)), "frt_selftest_path_host")
+        return out, st
+    a, fmt = image_array({"data": env_image})
+    desc = Image(a.shape[1], a.shape[0], fmt, 0, a.ctypes.data)
+    _check(lib().frt_selftest_path_host_env(ctypes.byref(view), ctypes.byref(params), pixels.ctypes.data, len(pixels),
+                                            ctypes.byref(desc), out.ctypes.data, ctypes.byref(st)),
+           "frt_selftest_path_host_env")
     return out, st
 
 
@@ -490,6 +547,17 @@ def selftest_mlt_paths_host(scene, nx, ny, seed, n):
     view = scene.view()
     _check(lib().frt_selftest_mlt_paths_host(ctypes.byref(view), nx, ny, seed, n, out.ctypes.data),
            "frt_selftest_mlt_paths_host")
+    return out
+
+
+def read_hdr(path):
+    """Radiance RGBE (.hdr) file -> (ny, nx, 3) float32, rows top to bottom
+    (frt_read_hdr: what the reference's image(file, STBI_HDR) holds)."""
+    nx, ny = ctypes.c_int32(0), ctypes.c_int32(0)
+    _check(lib().frt_read_hdr(os.fsencode(path), ctypes.byref(nx), ctypes.byref(ny), None), f"frt_read_hdr({path})")
+    out = np.zeros((ny.value, nx.value, 3), np.float32)
+    _check(lib().frt_read_hdr(os.fsencode(path), ctypes.byref(nx), ctypes.byref(ny), out.ctypes.data),
+           f"frt_read_hdr({path})")
     return out
 
 

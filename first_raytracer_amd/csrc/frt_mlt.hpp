@@ -136,7 +136,8 @@ FRT_HD void mlt_begin(MltPath &M, const DevScene &S, const PrndSource &src, int 
 FRT_HD bool mlt_beyond(const MltPath &M) { return !M.P.shadow && M.P.depth > kMltMaxPath; }
 
 // pssmlt::Li, one hit at a time.  Returns true when the path is finished.
-template <bool MATS = true>   // false: lambertian / diffuse_light scenes (see path_shade)
+// MATS false: lambertian / diffuse_light scenes (see path_shade); ENV: the environment is an image (kMatsEnv)
+template <bool MATS = true, bool ENV = false>
 FRT_HD bool mlt_shade(MltPath &M, const DevScene &S, const Hit<float> &h, const PrndSource &src, uint32_t &n_ext,
                       uint32_t &n_sh)
 {
@@ -148,7 +149,7 @@ FRT_HD bool mlt_shade(MltPath &M, const DevScene &S, const Hit<float> &h, const 
     }
     if (P.term) return true;                            // finished in the traversal loop
     if (h.prim < 0) {
-        P.L = P.L + P.beta * S.env;
+        P.L = P.L + P.beta * env_radiance<(ENV ? kMatsEnv : kMatsNone)>(S, P.rd);
         return true;
     }
     const f3 p = P.ro + h.t * P.rd;

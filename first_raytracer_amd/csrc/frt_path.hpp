@@ -137,6 +137,10 @@ struct DevScene {
     d3 cam64_o, cam64_llc, cam64_h, cam64_v, cam64_u, cam64_vv;   // the constructed camera in fp64
     double lens_r64;
     f3 env;
+    // environment_map over an image (frt_set_env_image): its texels (rgb, -) in a
+    // buffer of their own in HBM, rows top to bottom; env_nx = 0: the constant `env`
+    const float4 *env_texels;
+    int env_nx, env_ny;
 };
 
 template <typename R> struct Hit {
@@ -721,8 +725,12 @@ FRT_HD V3<R> prim_sample(const DevScene &S, int ref, V3<R> o, R u0, R u1, V3<R> 
 // textures, kMatsSpec the specular branch for modified_phong, metal and
 // dielectric, kMatsRough the rough conductor lobes (erf / erfinv, GGX slopes,
 // conductor Fresnel) -- the register-hungry part.  A scene runs the smallest
-// kernel covering its materials (frt_upload_scene).
+// kernel covering its materials (frt_upload_scene).  kMatsEnv, apart from the
+// material sets: the environment is an image (env_eval) -- only a context with
+// an environment image runs kernels compiled with it, so every other scene's
+// kernels hold no trace of the lookup.
 constexpr int kMatsNone = 0, kMatsTex = 1, kMatsSpec = 2, kMatsRough = 4, kMatsAll = 7;
+constexpr int kMatsEnv = 8;
 constexpr int kMatsSpecAny = kMatsSpec | kMatsRough;
 
 // ---- textures (texture.h:30-49), MATS kernels only ----
@@ -767,15 +775,43 @@ FRT_HD int imodulo(int a, int b) { const int r = a % b; return r < 0 ? r + b : r
 // texels hold the reference's linear value (FromSrgb(byte / 255) or the HDR
 // float) per texel, so only the index arithmetic runs here (fp32: a texel edge
 // can round to the neighbour, as the checker's cell edges do)
-template <typename R> FRT_HD f3 image_texel(const DevScene &S, float4 m4, R tu, R tv)
+template <typename R> FRT_HD int image_index(int nx, int ny, R tu, R tv)
 {
-    const int nx = f2i(m4.x), ny = f2i(m4.y);
     int i = x86_trunc(tu * (R)nx), j = x86_trunc(tv * (R)ny);
     if (i < 0 || i > nx) i = imodulo(i, nx);
     if (j < 0 || j > ny) j = imodulo(j, ny);
     if (i == nx) i = nx - 1;
     if (j == ny) j = ny - 1;
-    return xyz(S.texels[f2i(m4.z) + j * nx + i]);
+    return j * nx + i;
+}
+template <typename R> FRT_HD f3 image_texel(const DevScene &S, float4 m4, R tu, R tv)
+{
+    return xyz(S.texels[f2i(m4.z) + image_index(f2i(m4.x), f2i(m4.y), tu, tv)]);
+}
+// environment_map::eval over an image_texture (material.h:206-232): the ray's
+// direction -> (phi, theta) -> (u, v) -> image_texture::value.  One deviation,
+// fp32 only: normalize() can leave |d.y| an ulp above 1, where acosf gives NaN
+// and x86_trunc an arbitrary row; d.y is clamped to [-1, 1] there (the pole's
+// row).  The fp64 kernels follow the reference to the letter.
+template <typename R> FRT_HD V3<R> env_eval(const DevScene &S, V3<R> rd)
+{
+    const V3<R> d = normalize(rd);
+    R dy = d.y;
+    if constexpr (!kIsF64<R>) dy = vmin(vmax(dy, R(-1)), R(1));
+    R phi = vatan2(d.x, -d.z), theta = vacos(dy);
+    if (phi < R(0)) phi = phi + Cst<R>::pi * R(2);
+    if (theta < R(0)) theta = theta + Cst<R>::pi;
+    const R u = phi / (R(2) * Cst<R>::pi), v = theta / Cst<R>::pi;
+    const f3 c = xyz(S.env_texels[image_index(S.env_nx, S.env_ny, u, v)]);
+    return V3<R>{R(c.x), R(c.y), R(c.z)};
+}
+// Scene::env_map->eval for the ray direction rd that left the scene: the image
+// in kernels compiled with kMatsEnv (a context with an environment image runs
+// those, frt_set_env_image), the constant colour in all others.
+template <int MATS, typename R> FRT_HD V3<R> env_radiance(const DevScene &S, V3<R> rd)
+{
+    if constexpr ((MATS & kMatsEnv) != 0) return env_eval<R>(S, rd);
+    else return env_of<R>(S);
 }
 template <typename R>
 FRT_HD void apply_texture(const DevScene &S, int mat, int mtype, int ref, V3<R> p, R u, R v, float4 &m0, float4 &m1)
@@ -950,7 +986,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     }
     if (P.term) return true;                            // finished in the traversal loop
     if (h.prim < 0) {                                   // path.cpp:115 environment
-        P.L = P.L + P.beta * env_of<R>(S);
+        P.L = P.L + P.beta * env_radiance<MATS>(S, P.rd);
         return true;
     }
     const V3<R> p = P.ro + h.t * P.rd;
@@ -1067,12 +1103,11 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
 template <int MATS = kMatsAll, typename R>
 FRT_HD bool ao_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, uint32_t &n_sh)
 {
-    const V3<R> env = env_of<R>(S);
-    if (P.shadow) {                                     // visibility ray done
-        P.L = h.prim < 0 ? env : zero3<R>();
+    if (P.shadow) {                                     // visibility ray done: P.L holds the camera
+        if (h.prim >= 0) P.L = zero3<R>();              // ray's environment (ao.cpp:27 evaluates it with r)
         return true;
     }
-    P.L = env;
+    P.L = env_radiance<MATS>(S, P.rd);
     if (h.prim < 0) return true;
     const V3<R> p = P.ro + h.t * P.rd;
     V3<R> n;
@@ -1118,10 +1153,10 @@ FRT_HD bool ao_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, uint32
 
 // normals_renderer::Li (debug_renderer.h:8-17): the shading normal of the
 // camera hit, the environment on a miss.
-template <typename R> FRT_HD bool normals_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h)
+template <int MATS = kMatsAll, typename R> FRT_HD bool normals_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h)
 {
     if (h.prim < 0) {
-        P.L = env_of<R>(S);
+        P.L = env_radiance<MATS>(S, P.rd);
         return true;
     }
     const V3<R> p = P.ro + h.t * P.rd;
@@ -1137,7 +1172,7 @@ template <int KIND, int MATS, typename R>
 FRT_HD bool shade_kind(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
     if constexpr (KIND == FRT_INTEGRATOR_AO) return ao_shade<MATS>(P, S, h, n_sh);
-    else if constexpr (KIND == FRT_INTEGRATOR_NORMALS) return normals_shade(P, S, h);
+    else if constexpr (KIND == FRT_INTEGRATOR_NORMALS) return normals_shade<MATS>(P, S, h);
     else return path_shade<MATS>(P, S, h, max_depth, n_ext, n_sh);
 }
 

@@ -19,6 +19,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -544,7 +545,7 @@ __device__ __forceinline__ Hit<float> trace_any(const DevScene &S, const PathSta
 
 // bootstrap: sc of n_init independent eye paths (pssmlt.cpp:303-312); the host
 // sums them in a fixed order
-template <int STACK, int WORLD, bool MATS>
+template <int STACK, int WORLD, bool MATS, bool ENV = false>
 __global__ __launch_bounds__(kBlock) void mlt_bootstrap(const DevScene S0, int nx, int ny, uint32_t seed, int n_init,
                                                         float *sc)
 {
@@ -559,9 +560,9 @@ __global__ __launch_bounds__(kBlock) void mlt_bootstrap(const DevScene S0, int n
     mlt_begin(M, S, src, nx, ny);
     uint32_t ne = 0, ns = 0;
     for (;;) {
-        if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * S.env; break; }
+        if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * env_radiance<(ENV ? kMatsEnv : kMatsNone)>(S, M.P.rd); break; }
         const Hit<float> h = trace_any<WORLD, STACK>(S, M.P, stk);
-        if (mlt_shade<MATS>(M, S, h, src, ne, ns)) break;
+        if (mlt_shade<MATS, ENV>(M, S, h, src, ne, ns)) break;
     }
     sc[i] = fmaxf(fmaxf(M.P.L.x, M.P.L.y), M.P.L.z);
 }
@@ -604,7 +605,7 @@ __global__ void mlt_film_to_float(const unsigned long long *__restrict__ acc, fl
 #endif                           // +17 % over the compiler's own allocation (profiles/r01_expmlt1.txt);
                                  // round 4's kernel: 4 waves 690.8 ms, 5 waves 700.5, 6 waves 783.9
                                  // (same call, profiles/r04/r04g); experiment builds vary it
-template <int STACK, int WORLD, bool LDS_SCENE, bool MATS>
+template <int STACK, int WORLD, bool LDS_SCENE, bool MATS, bool ENV = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_EXP_MLT_WAVES))) void mlt_megakernel(
     const DevScene S0, const MltWork W)
 {
@@ -676,12 +677,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_EXP_
             FRT_DIAG_TICK(4);
             pending = false;
             if (beyond) {                               // pssmlt.cpp:151, :276
-                M.P.L = M.P.L + M.P.beta * S.env;
+                M.P.L = M.P.L + M.P.beta * env_radiance<(ENV ? kMatsEnv : kMatsNone)>(S, M.P.rd);
                 beyond = false;
                 done = true;
             } else {
                 uint32_t ne = 0, ns = 0;
-                done = mlt_shade<MATS>(M, S, T.h, source(), ne, ns);
+                done = mlt_shade<MATS, ENV>(M, S, T.h, source(), ne, ns);
                 n_ext += ne; n_sh += ns;
                 next_ray = !done;
             }
@@ -850,6 +851,12 @@ struct frt_ctx {
     int n_tris = 0, n_spheres = 0, n_list = 0;
     bool has_spec_mats = false;   // a non-lambertian scattering material or a texture: MATS kernels
     int mats = kMatsNone;         // kMats* mask of the scene's material set (pick_launcher)
+    // frt_set_env_image: the environment image's texels in a device buffer of their own, kept
+    // across uploads.  A context with one renders with the kernels compiled with the lookup
+    // (kMatsEnv, from frt_render_mats.hip); without one every scene keeps its kernels.
+    float4 *env_texels = nullptr;
+    int env_nx = 0, env_ny = 0;
+    uint64_t env_hash = 0;        // of the texels (frt_render_multi: every context must hold the same image)
     bool has_metal = false;       // ao::Li cannot sample metal (constant_pdf::generate throws, pdf.h:195-198)
     size_t scene_lds_bytes = 0;                         // LDS copy with the binary nodes
     size_t scene_lds_bytes_oct = 0;                     // ... with the 8 octant copies of the binary nodes
@@ -992,7 +999,7 @@ static int pick_launcher_t(const frt_ctx *c, int flags, Launcher &L)
     // item state moved to LDS; the compiler's 4 waves win 2 % at 64 spp but lose
     // 10 % at the bench's 512 spp -- 337 vs 307 ms, same call --, so the cap stays:
     // profiles/r02/r02_ab_cornell_knobs.jsonl, r02_ab_cornell_512spp.jsonl.)
-    int waves = (MATS & kMatsSpecAny) ? (lds ? 4 : 5) : MATS == kMatsTex && lds ? 0 : lds ? 5 : 6;
+    int waves = (MATS & kMatsSpecAny) ? (lds ? 4 : 5) : (MATS & ~kMatsEnv) == kMatsTex && lds ? 0 : lds ? 5 : 6;
     // the lambertian 4-wide HBM plan: 7 waves (round 5; the binary HBM fallback keeps 6)
     const bool wide = !lds && c->has_bvh4 && !(flags & FRT_FLAG_BVH2) && bvh4_stack_fits(c->depth4, kBvh4LdsStack);
     if (MATS == kMatsNone && wide) waves = 7;
@@ -1032,11 +1039,12 @@ static int pick_launcher_t(const frt_ctx *c, int flags, Launcher &L)
     return FRT_OK;
 }
 // AO / normals: the default plans only (LDS-resident binary BVH, HBM 4-wide or
-// binary), register caps as for path; ao keeps the specular generate() code.
-template <int KIND>
+// binary), register caps as for path; ao keeps the specular generate() code
+// (M = kMatsAll), normals has none (kMatsNone); a context with an environment
+// image runs both with kMatsEnv (the lookup on a miss).
+template <int KIND, int M>
 static int pick_launcher_kind(const frt_ctx *c, int flags, Launcher &L)
 {
-    constexpr int M = KIND == FRT_INTEGRATOR_AO ? kMatsAll : kMatsNone;
     if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, M, KIND>(0); return FRT_OK; }
     const int d = c->stack_needed;
     const size_t sb = c->scene_lds_bytes;
@@ -1076,25 +1084,28 @@ static int pick_launcher_f64_t(const frt_ctx *c, Launcher &L)
         return FRT_OK;
     }
     const int d = c->stack_needed;
-    if (d < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, kMatsAll, FRT_INTEGRATOR_PATH, double>(0);
-    else if (d < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, kMatsAll, FRT_INTEGRATOR_PATH, double>(0);
+    constexpr int kAll = kMatsAll | (MATS & kMatsEnv);
+    if (d < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, kAll, FRT_INTEGRATOR_PATH, double>(0);
+    else if (d < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, kAll, FRT_INTEGRATOR_PATH, double>(0);
     else return FRT_E_UNSUPPORTED;
     return FRT_OK;
 }
-template <int STACK, int WORLD, bool LDS, bool MATS>
+template <int STACK, int WORLD, bool LDS, bool MATS, bool ENV = false>
 static void mlt_kernels_t(const void **boot, const void **chains)
 {
-    *boot = reinterpret_cast<const void *>(&mlt_bootstrap<STACK, WORLD, MATS>);
-    *chains = reinterpret_cast<const void *>(&mlt_megakernel<STACK, WORLD, LDS, MATS>);
+    *boot = reinterpret_cast<const void *>(&mlt_bootstrap<STACK, WORLD, MATS, ENV>);
+    *chains = reinterpret_cast<const void *>(&mlt_megakernel<STACK, WORLD, LDS, MATS, ENV>);
 }
 
 // the material unit's entry points (frt_render_mats.hip)
 namespace frt_mats {
 // path (KIND = FRT_INTEGRATOR_PATH, fp32), fp64 path (f64) or AO: the plan for
-// the scene's material set c->mats (!= kMatsNone)
+// the scene's material set c->mats (!= kMatsNone); and every integrator of a
+// context with an environment image (the kMatsEnv kernels)
 int pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L);
-// PSS-MLT with the material branch, for the (stack, world, lds) plans of render_mlt
-int mlt(int stack, int world, bool lds, const void **boot, const void **chains);
+// PSS-MLT with the material branch or (env) the environment image, for the
+// (stack, world, lds) plans of render_mlt
+int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);
 }  // namespace frt_mats
 
 #if defined(FRT_TU_LDS)
@@ -1114,9 +1125,20 @@ int frt_lds::mlt_oct(int stack, const void **boot, const void **chains)
     return FRT_OK;
 }
 #elif defined(FRT_TU_MATS)
+// a context with an environment image: two material sets carry the lookup --
+// textures alone (lambertian and textured scenes) and every material
+static int pick_env(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L)
+{
+    if (integrator == FRT_INTEGRATOR_AO) return pick_launcher_kind<FRT_INTEGRATOR_AO, kMatsAll | kMatsEnv>(c, flags, L);
+    if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsEnv>(c, flags, L);
+    if (f64) return pick_launcher_f64_t<kMatsAll | kMatsEnv>(c, L);
+    if ((c->mats & ~kMatsTex) == 0) return pick_launcher_t<kMatsTex | kMatsEnv>(c, flags, L);
+    return pick_launcher_t<kMatsAll | kMatsEnv>(c, flags, L);
+}
 int frt_mats::pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L)
 {
-    if (integrator == FRT_INTEGRATOR_AO) return pick_launcher_kind<FRT_INTEGRATOR_AO>(c, flags, L);
+    if (c->env_texels) return pick_env(c, integrator, flags, f64, L);
+    if (integrator == FRT_INTEGRATOR_AO) return pick_launcher_kind<FRT_INTEGRATOR_AO, kMatsAll>(c, flags, L);
     if (f64) {
         switch (c->mats) {
         case kMatsNone: return pick_launcher_f64_t<kMatsNone>(c, L);   // BVH worlds: kMatsAll kernels
@@ -1133,19 +1155,25 @@ int frt_mats::pick(const frt_ctx *c, int integrator, int flags, bool f64, Launch
     default: return pick_launcher_t<kMatsAll>(c, flags, L);
     }
 }
-int frt_mats::mlt(int stack, int world, bool lds, const void **boot, const void **chains)
+template <bool MATS, bool ENV>
+static int mlt_pick(int stack, int world, bool lds, const void **boot, const void **chains)
 {
-    if (world == FRT_WORLD_LIST) mlt_kernels_t<16, FRT_WORLD_LIST, false, true>(boot, chains);
-    else if (world == kWorldBvh4) mlt_kernels_t<kBvh4LdsStack, kWorldBvh4, false, true>(boot, chains);
-    else if (world == kWorldBvh2Oct && stack == 8) mlt_kernels_t<8, kWorldBvh2Oct, true, true>(boot, chains);
-    else if (world == kWorldBvh2Oct && stack == 16) mlt_kernels_t<16, kWorldBvh2Oct, true, true>(boot, chains);
-    else if (lds && stack == 8) mlt_kernels_t<8, FRT_WORLD_BVH, true, true>(boot, chains);
-    else if (lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, true, true>(boot, chains);
-    else if (!lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, false, true>(boot, chains);
-    else if (!lds && stack == 32) mlt_kernels_t<32, FRT_WORLD_BVH, false, true>(boot, chains);
-    else if (!lds && stack == 64) mlt_kernels_t<64, FRT_WORLD_BVH, false, true>(boot, chains);
+    if (world == FRT_WORLD_LIST) mlt_kernels_t<16, FRT_WORLD_LIST, false, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh4) mlt_kernels_t<kBvh4LdsStack, kWorldBvh4, false, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh2Oct && stack == 8) mlt_kernels_t<8, kWorldBvh2Oct, true, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh2Oct && stack == 16) mlt_kernels_t<16, kWorldBvh2Oct, true, MATS, ENV>(boot, chains);
+    else if (lds && stack == 8) mlt_kernels_t<8, FRT_WORLD_BVH, true, MATS, ENV>(boot, chains);
+    else if (lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, true, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 32) mlt_kernels_t<32, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 64) mlt_kernels_t<64, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
     else return FRT_E_UNSUPPORTED;
     return FRT_OK;
+}
+// (an environment image always takes the material branch: one chain kernel per plan carries the lookup)
+int frt_mats::mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains)
+{
+    return env ? mlt_pick<true, true>(stack, world, lds, boot, chains) : mlt_pick<true, false>(stack, world, lds, boot, chains);
 }
 #else   // the main unit: everything else
 
@@ -1217,6 +1245,7 @@ extern "C" int frt_destroy(frt_ctx *c)
     if (c->wave_rays) (void)hipFree(c->wave_rays);
     if (c->slots_out) (void)hipFree(c->slots_out);
     if (c->splat) (void)hipFree(c->splat);
+    if (c->env_texels) (void)hipFree(c->env_texels);
     free_comms(c);
     if (c->gather) (void)hipFree(c->gather);
     if (c->film_dev) (void)hipFree(c->film_dev);
@@ -1533,6 +1562,47 @@ static bool build_bvh4(FlatScene &F, int root_ref)
 }
 
 // f64: also build the fp64 records of the fp64 kernels (DESIGN.md "Precision")
+// image_texture texels: the reference's value per texel (texture.h:76-87: the float of an
+// HDR image, FromSrgb(byte / 255.0) in double otherwise, util.h:62-66) rounded to fp32,
+// appended to `out` (scene textures and the environment image)
+static void append_texels(const frt_image &im, std::vector<float4> &out)
+{
+    const size_t n = (size_t)im.nx * im.ny;
+    auto srgb = [](double v) { return v <= 0.04045 ? v * (1.0 / 12.92) : std::pow((v + 0.055) * (1.0 / 1.055), 2.4); };
+    for (size_t q = 0; q < n; ++q) {
+        double c[3];
+        for (int ch = 0; ch < 3; ++ch)
+            c[ch] = im.format == FRT_IMAGE_F32 ? (double)static_cast<const float *>(im.data)[3 * q + ch]
+                                               : srgb(static_cast<const uint8_t *>(im.data)[3 * q + ch] / 255.0);
+        out.push_back(make_float4((float)c[0], (float)c[1], (float)c[2], 0.0f));
+    }
+}
+// frt_set_env_image / the self-test: validate the image and convert it.  PSS-MLT's
+// splats assume contributions >= 0, so negative and non-finite texels are refused.
+static int env_texels_of(const frt_image *img, std::vector<float4> &out, std::string &err)
+{
+    if (img->nx <= 0 || img->ny <= 0) { err = "environment image: nx and ny must be positive"; return FRT_E_INVALID; }
+    if (!img->data) { err = "environment image: null data"; return FRT_E_INVALID; }
+    if (img->format != FRT_IMAGE_SRGB8 && img->format != FRT_IMAGE_F32) {
+        err = "environment image: format must be FRT_IMAGE_SRGB8 or FRT_IMAGE_F32";
+        return FRT_E_INVALID;
+    }
+    if ((size_t)img->nx * img->ny > (size_t)INT32_MAX) { err = "environment image larger than 2^31 texels"; return FRT_E_UNSUPPORTED; }
+    out.clear();
+    out.reserve((size_t)img->nx * img->ny);
+    append_texels(*img, out);
+    for (size_t q = 0; q < out.size(); ++q) {
+        const float v[3] = {out[q].x, out[q].y, out[q].z};
+        for (int ch = 0; ch < 3; ++ch)
+            if (!(v[ch] >= 0.0f && v[ch] <= FLT_MAX)) {
+                err = "environment image: texel (" + std::to_string(q % img->nx) + ", " + std::to_string(q / img->nx) +
+                      ") is negative or not finite";
+                return FRT_E_INVALID;
+            }
+    }
+    return FRT_OK;
+}
+
 static int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64)
 {
     auto fail = [&](int code, const std::string &m) { err = m; return code; };
@@ -1751,8 +1821,7 @@ static int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &er
         F.smat[k] = sv->sphere_material[k];
         if (F.smat[k] < 0 || F.smat[k] >= nm) return fail(FRT_E_INVALID, "scene view: bad sphere material");
     }
-    // image_texture texels: the reference's value per texel (texture.h:76-87: the float of an
-    // HDR image, FromSrgb(byte / 255.0) in double otherwise, util.h:62-66) rounded to fp32
+    // image_texture texels (append_texels)
     std::vector<int> image_off(std::max(sv->n_images, 0), -1);
     for (int i = 0; i < nm; ++i) {
         if (sv->materials[i].texture != FRT_TEX_IMAGE) continue;
@@ -1762,14 +1831,7 @@ static int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &er
         const size_t n = (size_t)im.nx * im.ny;
         if (F.texels.size() + n > (size_t)INT32_MAX) return fail(FRT_E_UNSUPPORTED, "images larger than 2^31 texels");
         image_off[k] = (int)F.texels.size();
-        auto srgb = [](double v) { return v <= 0.04045 ? v * (1.0 / 12.92) : std::pow((v + 0.055) * (1.0 / 1.055), 2.4); };
-        for (size_t q = 0; q < n; ++q) {
-            double c[3];
-            for (int ch = 0; ch < 3; ++ch)
-                c[ch] = im.format == FRT_IMAGE_F32 ? (double)static_cast<const float *>(im.data)[3 * q + ch]
-                                                   : srgb(static_cast<const uint8_t *>(im.data)[3 * q + ch] / 255.0);
-            F.texels.push_back(make_float4((float)c[0], (float)c[1], (float)c[2], 0.0f));
-        }
+        append_texels(im, F.texels);
     }
     F.mats.assign(kMatStride * (size_t)nm, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (int i = 0; i < nm; ++i) {
@@ -1866,6 +1928,40 @@ static int upload_vec(frt_ctx *c, const std::vector<T> &v, P *dst)
     return FRT_OK;
 }
 
+// Scene::env_map as environment_map(image_texture): state of the context like
+// the precision.  The texels go to a device buffer of their own (the LDS scene
+// copy is not touched); renders after this call run the kernels compiled with
+// the lookup (kMatsEnv: frt_mats::pick, frt_mats::mlt), NULL returns to the
+// uploaded view's env_color and to the kernels the scene ran before.
+extern "C" int frt_set_env_image(frt_ctx *c, const frt_image *img)
+{
+    if (!c) return FRT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    float4 *dev = nullptr;
+    int nx = 0, ny = 0;
+    uint64_t hash = 0;
+    if (img) {
+        std::vector<float4> tex;
+        std::string err;
+        const int rc = env_texels_of(img, tex, err);
+        if (rc != FRT_OK) return set_err(c, rc, err);
+        HIPCHK(c, hipMalloc((void **)&dev, tex.size() * sizeof(float4)));
+        if (hipMemcpy(dev, tex.data(), tex.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return set_err(c, FRT_E_HIP, "frt_set_env_image: copy to the device failed");
+        }
+        nx = img->nx; ny = img->ny;
+        hash = 1469598103934665603ull;   // FNV-1a over the converted texels
+        const unsigned char *b = reinterpret_cast<const unsigned char *>(tex.data());
+        for (size_t i = 0; i < tex.size() * sizeof(float4); ++i) hash = (hash ^ b[i]) * 1099511628211ull;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // no render of this context still reads the old buffer
+    if (c->env_texels) (void)hipFree(c->env_texels);
+    c->env_texels = dev; c->env_nx = nx; c->env_ny = ny; c->env_hash = hash;
+    c->S.env_texels = dev; c->S.env_nx = nx; c->S.env_ny = ny;
+    return FRT_OK;
+}
+
 extern "C" int frt_upload_scene(frt_ctx *c, const frt_scene_view *sv)
 {
     if (!c || !sv) return FRT_E_INVALID;
@@ -1880,6 +1976,7 @@ extern "C" int frt_upload_scene(frt_ctx *c, const frt_scene_view *sv)
     free_scene(c);
     c->S = F.meta;
     DevScene &S = c->S;
+    S.env_texels = c->env_texels; S.env_nx = c->env_nx; S.env_ny = c->env_ny;   // context state, kept across uploads
     int rc;
     if ((rc = upload_vec(c, F.nodes, &S.nodes)) || (rc = upload_vec(c, F.nodes4, &S.nodes4)) ||
         (rc = upload_vec(c, F.nodes_oct, &S.nodes_oct)) ||
@@ -1939,7 +2036,7 @@ static DevScene host_scene(const FlatScene &F)
 }
 
 // the self-test's per-pixel loop in precision R (fp64: the binary tree or the list)
-template <typename R>
+template <typename R, int MATS = kMatsAll>
 static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_render_params *p, const int32_t *pixels,
                             int npix, bool wide, std::vector<int> &stack, float *out_rgb, uint64_t cnt[3])
 {
@@ -1963,9 +2060,9 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
                     h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
                 }
                 n_ext = n_sh = 0;
-                const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade(P, S, h, n_sh)
-                                  : p->integrator == FRT_INTEGRATOR_NORMALS ? normals_shade(P, S, h)
-                                  : path_shade(P, S, h, p->max_depth, n_ext, n_sh);
+                const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade<MATS>(P, S, h, n_sh)
+                                  : p->integrator == FRT_INTEGRATOR_NORMALS ? normals_shade<MATS>(P, S, h)
+                                  : path_shade<MATS>(P, S, h, p->max_depth, n_ext, n_sh);
                 cnt[1] += n_ext; cnt[2] += n_sh;
                 if (done) break;
             }
@@ -1983,6 +2080,12 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
 extern "C" int frt_selftest_path_host(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
                                       int npix, float *out_rgb, frt_stats *st)
 {
+    return frt_selftest_path_host_env(sv, p, pixels, npix, nullptr, out_rgb, st);
+}
+// ... with an environment image (frt_set_env_image's validation and conversion; NULL = none)
+extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
+                                          int npix, const frt_image *env, float *out_rgb, frt_stats *st)
+{
     if (!sv || !p || !pixels || !out_rgb || npix < 0 || p->spp <= 0 || p->nx <= 0 || p->ny <= 0) return FRT_E_INVALID;
     for (int i = 0; i < npix; ++i)
         if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
@@ -1994,12 +2097,21 @@ extern "C" int frt_selftest_path_host(const frt_scene_view *sv, const frt_render
     if (p->integrator == FRT_INTEGRATOR_AO)
         for (int i = 0; i < sv->n_materials; ++i)
             if (sv->materials[i].type == FRT_MAT_METAL) return FRT_E_UNSUPPORTED;
-    const DevScene S = host_scene(F);
+    DevScene S = host_scene(F);
+    std::vector<float4> env_tex;
+    if (env) {
+        const int erc = env_texels_of(env, env_tex, err);
+        if (erc != FRT_OK) return erc;
+        S.env_texels = env_tex.data(); S.env_nx = env->nx; S.env_ny = env->ny;
+    }
     std::vector<int> stack(std::max(F.depth + 1, kSelftestStack));
     const bool wide = !f64 && S.world_kind == FRT_WORLD_BVH && F.has4 && !(p->flags & FRT_FLAG_BVH2) &&
                       bvh4_stack_fits(F.depth4, kSelftestStack);
     uint64_t cnt[3] = {0, 0, 0};   // camera, extension, shadow
-    if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    constexpr int kEnvAll = kMatsAll | kMatsEnv;   // with an image: the code of the kMatsEnv kernels
+    if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (env) selftest_pixels<float, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else selftest_pixels<float>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     if (st) {
         memset(st, 0, sizeof(*st));
@@ -2031,7 +2143,7 @@ extern "C" int frt_selftest_mlt_paths_host(const frt_scene_view *sv, int nx, int
         mlt_begin(M, S, src, nx, ny);
         uint32_t ne = 0, ns = 0;
         for (;;) {
-            if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * S.env; break; }
+            if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * env_of<float>(S); break; }
             const Hit<float> h = (S.world_kind == FRT_WORLD_LIST)
                               ? trace<FRT_WORLD_LIST, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data())
                               : trace<FRT_WORLD_BVH, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data());
@@ -2109,7 +2221,8 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
 static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
-    if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS>(c, flags, L);
+    if (c->env_texels) return frt_mats::pick(c, integrator, flags, f64, L);   // the kMatsEnv kernels
+    if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsNone>(c, flags, L);
     if (integrator == FRT_INTEGRATOR_AO || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
         return frt_mats::pick(c, integrator, flags, f64, L);   // every kernel with a material set
     if (f64) {   // a lambertian list world (BVH worlds' fp64 kernels carry every material: the other unit)
@@ -2228,9 +2341,9 @@ extern "C" int frt_trace_device(frt_ctx *c, const float *rays, int64_t n, float 
 // ---- PSS-MLT render: bootstrap b, then the chain megakernel splatting into dev_film ----
 // PSS-MLT kernels of a plan: the material branch from the material unit
 template <int STACK, int WORLD, bool LDS = false>
-static void mlt_kernels(bool mats, const void **boot, const void **chains)
+static void mlt_kernels(bool mats, bool env, const void **boot, const void **chains)
 {
-    if (mats) frt_mats::mlt(STACK, WORLD, LDS, boot, chains);
+    if (mats || env) frt_mats::mlt(STACK, WORLD, LDS, env, boot, chains);
     else if constexpr (WORLD == kWorldBvh2Oct && kSplitLds) frt_lds::mlt_oct(STACK, boot, chains);
     else mlt_kernels_t<STACK, WORLD, LDS, false>(boot, chains);
 }
@@ -2279,18 +2392,19 @@ static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, h
                            !(p->flags & FRT_FLAG_NO_LDS_SCENE);
     // the octant node copies when they fit, as the path kernels (round 5: the chain kernel used the planar tree)
     const bool oct = lds_scene && !(p->flags & FRT_FLAG_NO_OCT) && c->scene_lds_bytes_oct <= kLdsOctBytes;
-    if (c->world_kind == FRT_WORLD_LIST) { stack = 0; mlt_kernels<16, FRT_WORLD_LIST>(c->has_spec_mats, &kboot, &kchain); }
+    const bool env = c->env_texels != nullptr;   // the chain kernels with the environment lookup
+    if (c->world_kind == FRT_WORLD_LIST) { stack = 0; mlt_kernels<16, FRT_WORLD_LIST>(c->has_spec_mats, env, &kboot, &kchain); }
     else if (!lds_scene && c->has_bvh4 && !(p->flags & FRT_FLAG_BVH2) && bvh4_stack_fits(c->depth4, kBvh4LdsStack)) {
         stack = kBvh4LdsStack;
-        mlt_kernels<kBvh4LdsStack, kWorldBvh4>(c->has_spec_mats, &kboot, &kchain);
+        mlt_kernels<kBvh4LdsStack, kWorldBvh4>(c->has_spec_mats, env, &kboot, &kchain);
     }
-    else if (oct && d < 8) { stack = 8; mlt_kernels<8, kWorldBvh2Oct, true>(c->has_spec_mats, &kboot, &kchain); }
-    else if (oct) { stack = 16; mlt_kernels<16, kWorldBvh2Oct, true>(c->has_spec_mats, &kboot, &kchain); }
-    else if (lds_scene && d < 8) { stack = 8; mlt_kernels<8, FRT_WORLD_BVH, true>(c->has_spec_mats, &kboot, &kchain); }
-    else if (lds_scene) { stack = 16; mlt_kernels<16, FRT_WORLD_BVH, true>(c->has_spec_mats, &kboot, &kchain); }
-    else if (d < 16) { stack = 16; mlt_kernels<16, FRT_WORLD_BVH>(c->has_spec_mats, &kboot, &kchain); }
-    else if (d < 32) { stack = 32; mlt_kernels<32, FRT_WORLD_BVH>(c->has_spec_mats, &kboot, &kchain); }
-    else if (d < 64) { stack = 64; mlt_kernels<64, FRT_WORLD_BVH>(c->has_spec_mats, &kboot, &kchain); }
+    else if (oct && d < 8) { stack = 8; mlt_kernels<8, kWorldBvh2Oct, true>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (oct) { stack = 16; mlt_kernels<16, kWorldBvh2Oct, true>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (lds_scene && d < 8) { stack = 8; mlt_kernels<8, FRT_WORLD_BVH, true>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (lds_scene) { stack = 16; mlt_kernels<16, FRT_WORLD_BVH, true>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (d < 16) { stack = 16; mlt_kernels<16, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (d < 32) { stack = 32; mlt_kernels<32, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
+    else if (d < 64) { stack = 64; mlt_kernels<64, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
     else return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
     const size_t lds_boot = (size_t)stack * kBlock * sizeof(int);
     const size_t lds = lds_boot + (size_t)kChainWords * kBlock * sizeof(int) +
@@ -2678,6 +2792,10 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
     frt_ctx *c0 = ctxs[0];
     if (!params_ok(p) || p->shard_count != 1 || p->shard_index != 0)
         return set_err(c0, FRT_E_INVALID, "frt_render_multi: params must describe the whole frame (shard 0 of 1)");
+    for (int i = 1; i < n; ++i)   // the environment image is context state: every member needs the same one
+        if (ctxs[i]->env_nx != c0->env_nx || ctxs[i]->env_ny != c0->env_ny || ctxs[i]->env_hash != c0->env_hash)
+            return set_err(c0, FRT_E_INVALID, "frt_render_multi: the contexts hold different environment images "
+                                              "(frt_set_env_image on every one)");
     const auto t_start = std::chrono::steady_clock::now();
     const bool mlt = p->integrator == FRT_INTEGRATOR_PSSMLT;
     const size_t film_n = (size_t)p->nx * p->ny * 3;

@@ -412,6 +412,7 @@ struct frt_host_scene {
     double env[3] = {0, 0, 0};
     std::vector<frt_image> images;                    // data points into image_data
     std::vector<std::vector<uint8_t>> image_data;
+    int env_image = -1;      // frt_scene_set_env_image: index into images, -1 = the constant env
     int bvh_depth = 0;
     double load_ms = 0, build_ms = 0;
     bool finished = true;    // false between frt_scene_new and frt_scene_finish
@@ -977,6 +978,22 @@ extern "C" int frt_scene_add_image(frt_host_scene *s, const frt_image *img, int 
     s->images.push_back(c);
     *index = (int)s->images.size() - 1;
     return FRT_OK;
+}
+
+// Scene::env_map over image `index` (material.h:206-244); the context takes it
+// through frt_scene_env_image + frt_set_env_image, the scene view is unchanged
+extern "C" int frt_scene_set_env_image(frt_host_scene *s, int index)
+{
+    if (!s || index < -1 || index >= (int)s->images.size()) return FRT_E_INVALID;
+    s->env_image = index;
+    return FRT_OK;
+}
+extern "C" int frt_scene_env_image(const frt_host_scene *s, frt_image *out)
+{
+    if (!s || !out) return FRT_E_INVALID;
+    if (s->env_image < 0) return 0;
+    *out = s->images[s->env_image];
+    return 1;
 }
 
 extern "C" int frt_scene_finish(frt_host_scene *s, int world_kind)

@@ -4,11 +4,13 @@
 //
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
 //              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals] [--chains 262144]
-//              [--env r,g,b] [--out out.pfm] [--png out.png] [--bvh reference|sah]
+//              [--env r,g,b | --env-map file.hdr] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
 // --env: constant environment colour (the reference scenes' is black).
+// --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
+//   image_texture, material.h:206-244); exclusive with --env.
 // --png: also the tonemapped display image (viewer::add_sample bytes, image::save_image).
 // --bvh sah: rebuild the scene's BVH with the binned SAH builder (faster traversal;
 //   exact-t ties then follow that tree's order instead of create_bvh's).
@@ -21,7 +23,7 @@
 
 int main(int argc, char **argv)
 {
-    std::string scene = "cornell", obj, out = "out.pfm", integrator = "path", png, bvh = "reference";
+    std::string scene = "cornell", obj, out = "out.pfm", integrator = "path", png, bvh = "reference", env_map;
     int nx = 512, ny = 512, gpus = 1, chains = 1 << 18;
     long ns = 100;
     unsigned seed = 0;
@@ -48,14 +50,17 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%lf,%lf,%lf", &env[0], &env[1], &env[2]) != 3) return 2;
             has_env = true;
         }
+        else if (a == "--env-map") env_map = next();
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
+    if (has_env && !env_map.empty()) { std::fprintf(stderr, "--env and --env-map exclude each other\n"); return 2; }
     try {
         std::printf("Resolution: %dx%d\nSetting number of samples to %ld\n", nx, ny, ns);
         const std::string kind = scene == "cornell" ? "cornell_box_obj" : scene == "veach" ? "veach_mis" : "obj_smooth";
         frt::Scene s(kind, obj, double(nx) / double(ny));
         if (has_env) s.set_env(env[0], env[1], env[2]);
+        if (!env_map.empty()) s.set_env_map(env_map);
         if (bvh == "sah") s.build_bvh_sah();
         else if (bvh != "reference") { std::fprintf(stderr, "unknown --bvh %s\n", bvh.c_str()); return 2; }
         std::printf("BVH construction took me %g seconds (%d triangles, depth %d).\n", s.info().build_ms * 1e-3,

@@ -215,6 +215,24 @@ const char *frt_last_error(const frt_ctx *ctx);
  * scene) and by every render.  Default FRT_PRECISION_AUTO. */
 int frt_set_precision(frt_ctx *ctx, int precision);
 
+/* Scene::env_map as environment_map(image_texture) (material.h:206-244): on a
+ * miss every integrator returns the image's nearest texel in the ray's direction
+ * d = normalize(rd): phi = atan2(d.x, -d.z) (+ 2 pi when negative), theta =
+ * acos(d.y), (u, v) = (phi / 2 pi, theta / pi), then image_texture's index rule
+ * (row 0 = +y pole; FRT_IMAGE_SRGB8 or FRT_IMAGE_F32, converted as scene
+ * textures are).  The fp32 kernels clamp d.y to [-1, 1] first (normalize can
+ * leave it an ulp outside, where acosf is NaN); the fp64 kernels do not.
+ * State of the context like frt_set_precision: the texels are copied to the
+ * device during the call, kept across frt_upload_scene and read by every later
+ * render; NULL = back to the constant env_color of the uploaded view.  A context
+ * with an image renders with the kernels compiled for textures, every other
+ * context with the ones it used before.  FRT_E_INVALID (text in frt_last_error)
+ * for nx / ny <= 0, null data, an unknown format and for a negative or
+ * non-finite texel (PSS-MLT's splats need contributions >= 0).
+ * frt_render_multi: set the same image on every context; contexts that
+ * disagree fail with FRT_E_INVALID. */
+int frt_set_env_image(frt_ctx *ctx, const frt_image *img);
+
 /* Copy the scene to HBM (fp32 device layout, DESIGN.md "Data layout").  The
  * view's arrays are only read during the call. */
 int frt_upload_scene(frt_ctx *ctx, const frt_scene_view *scene);
@@ -319,6 +337,13 @@ int frt_scene_set_camera(frt_host_scene *s, const double *lookfrom, const double
 int frt_scene_set_env(frt_host_scene *s, const double *rgb);
 /* a decoded image (copied) for FRT_TEX_IMAGE materials; *index = its frt_material.image */
 int frt_scene_add_image(frt_host_scene *s, const frt_image *img, int *index);
+/* image `index` (frt_scene_add_image) is the scene's environment; -1 = the
+ * constant of frt_scene_set_env.  The scene view has no field for it (ABI 9):
+ * frt_scene_env_image gives the image to hand to frt_set_env_image: the scene's
+ * copy, valid until the scene is destroyed; it returns 1 with *out
+ * filled, or 0 and leaves *out alone when there is none. */
+int frt_scene_set_env_image(frt_host_scene *s, int index);
+int frt_scene_env_image(const frt_host_scene *s, frt_image *out);
 /* world_kind FRT_WORLD_BVH (create_bvh) or FRT_WORLD_LIST */
 int frt_scene_finish(frt_host_scene *s, int world_kind);
 /* GPU BVH builders: replace the finished scene's world
@@ -349,6 +374,14 @@ void frt_scene_destroy(frt_host_scene *s);
  * tessellated into k x k cells, written as OBJ + MTL. */
 int frt_write_tessellated_obj(const char *src_obj, int k, const char *dst_obj);
 
+/* Radiance RGBE (.hdr) reader: what stbi_loadf gives the reference's
+ * image(file, STBI_HDR) (image.cpp:16): rows top to bottom, 3 floats per texel,
+ * value = mantissa * 2^(e - 136), e == 0 -> 0; flat and new-style RLE scanlines,
+ * "-Y h +X w" orientation only (anything else: FRT_E_UNSUPPORTED).  rgb == NULL:
+ * sizes only; otherwise nx * ny * 3 floats.  FRT_E_IO: unreadable or truncated
+ * file; FRT_E_INVALID: not a Radiance file, bad header or bad scanline data. */
+int frt_read_hdr(const char *path, int32_t *nx, int32_t *ny, float *rgb);
+
 /* image_pfm::save_image layout (image.h:89-118), path used as given. */
 int frt_write_pfm(const char *path, int nx, int ny, const float *rgb);
 
@@ -375,6 +408,10 @@ int frt_write_image(const char *path, int nx, int ny, const uint8_t *rgb_u8, int
  *      render path: frt_render / frt_render_device never use it. ---- */
 int frt_selftest_path_host(const frt_scene_view *scene, const frt_render_params *p, const int32_t *pixels,
                            int npix, float *out_rgb, frt_stats *st);
+/* ... with an environment image (NULL = none), validated and converted as
+ * frt_set_env_image does and read as a render reads it */
+int frt_selftest_path_host_env(const frt_scene_view *scene, const frt_render_params *p, const int32_t *pixels,
+                               int npix, const frt_image *env, float *out_rgb, frt_stats *st);
 /* Same for PSS-MLT: n bootstrap-stream eye paths (frt_mlt.hpp) on the host;
  * out6 per path = film x, film y, r, g, b, scalar contribution. */
 int frt_selftest_mlt_paths_host(const frt_scene_view *scene, int nx, int ny, uint32_t seed, int n, float *out6);

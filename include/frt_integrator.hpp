@@ -56,6 +56,33 @@ public:
     }
     // Scene::env_map with another constant colour (material.h:206-232)
     void set_env(double r, double g, double b) { env_[0] = r; env_[1] = g; env_[2] = b; has_env_ = true; }
+    // Scene::env_map as environment_map(image) (material.h:206-244; main.cpp's
+    // open scenes load grace.hdr / ennis.hdr this way): a Radiance .hdr file, or a
+    // decoded image (copied).  The *_gpu integrators hand it to their contexts
+    // after the upload (frt_set_env_image).
+    void set_env_map(const std::string &hdr_path)
+    {
+        int32_t nx = 0, ny = 0;
+        check(frt_read_hdr(hdr_path.c_str(), &nx, &ny, nullptr), ("frt_read_hdr(" + hdr_path + ")").c_str());
+        env_data_.assign((size_t)nx * ny * 3 * sizeof(float), 0);
+        check(frt_read_hdr(hdr_path.c_str(), &nx, &ny, reinterpret_cast<float *>(env_data_.data())),
+              ("frt_read_hdr(" + hdr_path + ")").c_str());
+        env_image_ = frt_image{nx, ny, FRT_IMAGE_F32, 0, env_data_.data()};
+        has_env_image_ = true;
+    }
+    void set_env_map(const frt_image &img)
+    {
+        if (img.nx <= 0 || img.ny <= 0 || !img.data || (img.format != FRT_IMAGE_SRGB8 && img.format != FRT_IMAGE_F32))
+            throw error(FRT_E_INVALID, "set_env_map: bad image");
+        const size_t n = (size_t)img.nx * img.ny * 3 * (img.format == FRT_IMAGE_F32 ? sizeof(float) : 1);
+        const uint8_t *src = static_cast<const uint8_t *>(img.data);
+        env_data_.assign(src, src + n);
+        env_image_ = img;
+        env_image_.data = env_data_.data();
+        has_env_image_ = true;
+    }
+    // the environment image, or nullptr for the constant colour
+    const frt_image *env_map() const { return has_env_image_ ? &env_image_ : nullptr; }
     // replace the reference-topology BVH: binned SAH on the host, or the GPU
     // linear BVH on ctx's device (frt_scene_build_bvh_sah / _gpu)
     void build_bvh_sah()
@@ -73,6 +100,9 @@ public:
 private:
     double env_[3] = {0, 0, 0};
     bool has_env_ = false;
+    std::vector<uint8_t> env_data_;
+    frt_image env_image_{};
+    bool has_env_image_ = false;
     struct del { void operator()(frt_host_scene *s) const { frt_scene_destroy(s); } };
     std::unique_ptr<frt_host_scene, del> scene_;
     frt_host_scene_info info_{};
@@ -129,17 +159,19 @@ struct viewer {
     std::vector<double> fout_image;
 };
 
-// One frt_ctx per listed device with the scene uploaded (uploads run in
-// parallel, one host thread per device).
+// One frt_ctx per listed device with the scene uploaded and the environment
+// image (if any) set (uploads run in parallel, one host thread per device).
 class device_set {
 public:
-    device_set(const std::vector<int> &devices, const frt_scene_view &view) : ctx_(devices.size(), nullptr)
+    device_set(const std::vector<int> &devices, const frt_scene_view &view, const frt_image *env_map = nullptr)
+        : ctx_(devices.size(), nullptr)
     {
         std::vector<std::string> errs(devices.size());
         auto up = [&](size_t i) {
             try {
                 check(frt_create(devices[i], &ctx_[i]), "frt_create");
                 check(frt_upload_scene(ctx_[i], &view), "frt_upload_scene", ctx_[i]);
+                if (env_map) check(frt_set_env_image(ctx_[i], env_map), "frt_set_env_image", ctx_[i]);
             } catch (const std::exception &e) {
                 errs[i] = e.what();
             }
@@ -182,7 +214,7 @@ struct tile_gpu {
 
     void Render(Scene *scene, viewer *film)
     {
-        device_set gpus(devices, scene->view());
+        device_set gpus(devices, scene->view(), scene->env_map());
         frt_render_params p{};
         p.nx = film->nx; p.ny = film->ny; p.spp = (int)film->ns; p.seed = seed;
         p.max_depth = max_depth; p.integrator = INTEGRATOR; p.tile_size = tile_size;
@@ -215,7 +247,7 @@ struct pssmlt_gpu {
 
     void Render(Scene *scene, viewer *film)
     {
-        device_set gpus(devices, scene->view());
+        device_set gpus(devices, scene->view(), scene->env_map());
         frt_render_params p{};
         p.nx = film->nx; p.ny = film->ny; p.spp = (int)film->ns; p.seed = seed;
         p.max_depth = 10; p.integrator = FRT_INTEGRATOR_PSSMLT; p.tile_size = 32;
