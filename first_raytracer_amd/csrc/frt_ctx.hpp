@@ -1,0 +1,105 @@
+// frt_ctx.hpp -- the context behind the C-ABI's frt_ctx handle, the error
+// helpers, the residency rule of the launch plans and the few host functions
+// that cross the library's units.  Internal to libfrt.so.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "frt.h"
+#include "frt_kernels.hpp"
+
+struct ncclComm;   // rccl's communicator; only frt_multi.hip includes rccl.h
+
+struct frt_ctx {
+    int device = -1;
+    int n_cu = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    // scene
+    bool have_scene = false;
+    DevScene S{};
+    int world_kind = 0, stack_needed = 0;
+    bool has_bvh4 = false;        // nodes4 holds the 4-wide BVH4Q
+    int depth4 = 0;               // levels of that wide tree
+    int n_tris = 0, n_spheres = 0, n_list = 0;
+    bool has_spec_mats = false;   // a non-lambertian scattering material or a texture: MATS kernels
+    int mats = kMatsNone;         // kMats* mask of the scene's material set (pick_launcher)
+    // frt_set_env_image: the environment image's texels in a device buffer of their own, kept
+    // across uploads.  A context with one renders with the kernels compiled with the lookup
+    // (kMatsEnv, from frt_render_mats.hip); without one every scene keeps its kernels.
+    float4 *env_texels = nullptr;
+    int env_nx = 0, env_ny = 0;
+    uint64_t env_hash = 0;        // of the texels (frt_render_multi: every context must hold the same image)
+    bool has_metal = false;       // ao::Li cannot sample metal (constant_pdf::generate throws, pdf.h:195-198)
+    size_t scene_lds_bytes = 0;                         // LDS copy with the binary nodes
+    size_t scene_lds_bytes_oct = 0;                     // ... with the 8 octant copies of the binary nodes
+    int precision = FRT_PRECISION_AUTO;                 // frt_set_precision
+    bool has_f64 = false;                               // the scene's fp64 records are in HBM
+    double last_mlt_b = 0.0;
+    uint64_t mlt_rows = 0;        // chains whose state rows the last PSS-MLT render left in `partial`
+    std::vector<void *> scene_bufs;
+    // workspace
+    float *partial = nullptr; size_t partial_bytes = 0;
+    unsigned *counter = nullptr;
+    unsigned long long *wave_rays = nullptr; size_t wave_rays_n = 0;
+    float *slots_out = nullptr; size_t slots_out_bytes = 0;
+    unsigned long long *splat = nullptr; size_t splat_bytes = 0;   // PSS-MLT fixed-point splat film
+    // frt_render_multi on this context as shard 0: RCCL communicators over the
+    // member devices (one per member, cached while the device list is the
+    // same), the gather buffer and the device film
+    std::vector<int> comm_devs;
+    std::vector<ncclComm *> comms;   // ncclComm_t (frt_multi.hip)
+    float *gather = nullptr; size_t gather_bytes = 0;
+    float *film_dev = nullptr; size_t film_dev_bytes = 0;
+};
+
+#pragma GCC visibility push(hidden)
+inline int set_err(frt_ctx *c, int code, const std::string &m)
+{
+    if (c) c->err = m;
+    return code;
+}
+#define HIPCHK(ctx, x)                                                                             \
+    do {                                                                                           \
+        hipError_t e_ = (x);                                                                       \
+        if (e_ != hipSuccess)                                                                      \
+            return set_err(ctx, FRT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));       \
+    } while (0)
+
+// 4-wide traversal holds at most 3 pending siblings per level of the path
+inline bool bvh4_stack_fits(int depth4, int lds_entries) { return 3 * depth4 <= lds_entries + kBvh4Overflow; }
+#ifndef FRT_EXP_BVH4_LSTACK
+#define FRT_EXP_BVH4_LSTACK 12
+#endif
+// LDS entries of the 4-wide stack; deeper ones go to scratch.  12 since round 5
+// (was 16): 12 KiB of stack + 10 KiB of item state a block let 7 blocks share a
+// CU's 160 KiB, and the lambertian 4-wide kernel runs 7 waves/SIMD (72 VGPRs,
+// no spills since the SLP vectorizer is off): cornell_1m 360.3 -> 344.3 ms
+// (+4.6 %, same call, profiles/r05/r05i/ab_m.jsonl)
+constexpr int kBvh4LdsStack = FRT_EXP_BVH4_LSTACK;
+
+// Where a plan keeps the scene (every integrator's plan and the ray queries
+// decide it here): lds = the binary tree with the scene in LDS, oct = ... with
+// the per-octant node copies, wide = the 4-wide quantized tree from HBM.  List
+// worlds have no tree: all false.  The stack sizes stay with each plan.
+struct Residency { bool lds, oct, wide; };
+inline Residency residency(const frt_ctx *c, int flags)
+{
+    Residency r;
+    r.lds = c->world_kind == FRT_WORLD_BVH && c->stack_needed < kLdsMaxDepth && c->scene_lds_bytes <= kLdsSceneBytes &&
+            !(flags & FRT_FLAG_NO_LDS_SCENE);
+    r.oct = r.lds && !(flags & FRT_FLAG_NO_OCT) && c->scene_lds_bytes_oct <= kLdsOctBytes;
+    r.wide = !r.lds && c->has_bvh4 && !(flags & FRT_FLAG_BVH2) && bvh4_stack_fits(c->depth4, kBvh4LdsStack);
+    return r;
+}
+
+// frt_render.hip
+int eff_tile(const frt_render_params *p);
+bool params_ok(const frt_render_params *p);
+int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats);
+// frt_multi.hip
+void free_comms(frt_ctx *c);
+#pragma GCC visibility pop

@@ -3,7 +3,7 @@
 // kernels ("fp32 on the GPU, with an fp64 compile option for
 // debugging parity"; DESIGN.md "Precision").  All functions are
 // __host__ __device__ so the same code also runs in the host self tests
-// (frt_selftest_* in frt_render.hip).
+// (frt_selftest_* in frt_selftest.hip).
 //
 // Reference semantics restated (fp64 there), first_ray/:
 //   aabb::hit           aabb.h:14-31       (slab test, NaN-tolerant)

@@ -1,10 +1,24 @@
 // The library's fourth translation unit: the lambertian PSS-MLT chain kernels
-// of the octant LDS plan (C5), reached through frt_lds::mlt_oct (frt_render.hip
-// "launch plans").  Built with the machine scheduler's iterative-maxocc
-// strategy (Makefile, CHAINFLAGS); see the comment at kSplitLds.
-#define FRT_TU_CHAIN 1
-#undef FRT_DIAG
-#ifndef FRT_RENDER_SRC
-#define FRT_RENDER_SRC "frt_render.hip"
+// of the octant LDS plan (C5), reached through frt_lds::mlt_oct (frt_plans.hpp).
+// Built with the machine scheduler's iterative-maxocc strategy (Makefile,
+// CHAINFLAGS); see the comment at kSplitLds.
+// Diagnostic and no-split builds (recorded before FRT_DIAG is dropped) keep these
+// kernels in the main unit: this one then holds none.
+#if defined(FRT_DIAG) || defined(FRT_EXP_NO_LDS_SPLIT)
+#define FRT_OCT_IN_MAIN 1
 #endif
-#include FRT_RENDER_SRC
+#undef FRT_DIAG
+#include "frt_kernels.hpp"
+#include "frt_plans.hpp"
+
+int frt_lds::mlt_oct(int stack, const void **boot, const void **chains)
+{
+#if defined(FRT_OCT_IN_MAIN)
+    return FRT_E_UNSUPPORTED;
+#else
+    if (stack == 8) mlt_kernels_t<8, kWorldBvh2Oct, true, false>(boot, chains);
+    else if (stack == 16) mlt_kernels_t<16, kWorldBvh2Oct, true, false>(boot, chains);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+#endif
+}

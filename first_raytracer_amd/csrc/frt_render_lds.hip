@@ -1,11 +1,24 @@
 // The library's third translation unit: the lambertian path kernels of the
-// octant LDS plan (C2), reached through frt_lds::path_oct (frt_render.hip
-// "launch plans").  Built with the machine
-// scheduler's max-memory-clause strategy (Makefile, LDSFLAGS); see the comment
-// at kSplitLds.
-#define FRT_TU_LDS 1
-#undef FRT_DIAG
-#ifndef FRT_RENDER_SRC
-#define FRT_RENDER_SRC "frt_render.hip"
+// octant LDS plan (C2), reached through frt_lds::path_oct (frt_plans.hpp).
+// Built with the machine scheduler's max-memory-clause strategy (Makefile,
+// LDSFLAGS); see the comment at kSplitLds.
+// Diagnostic and no-split builds (recorded before FRT_DIAG is dropped) keep these
+// kernels in the main unit: this one then holds none.
+#if defined(FRT_DIAG) || defined(FRT_EXP_NO_LDS_SPLIT)
+#define FRT_OCT_IN_MAIN 1
 #endif
-#include FRT_RENDER_SRC
+#undef FRT_DIAG
+#include "frt_kernels.hpp"
+#include "frt_plans.hpp"
+
+int frt_lds::path_oct(int stack, int waves, size_t scene_bytes, Launcher &L)
+{
+#if defined(FRT_OCT_IN_MAIN)
+    return FRT_E_UNSUPPORTED;
+#else
+    if (stack == 8) L = bvh_launcher<8, true, kWorldBvh2Oct, kMatsNone>(waves, scene_bytes);
+    else if (stack == 16) L = bvh_launcher<16, true, kWorldBvh2Oct, kMatsNone>(waves, scene_bytes);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+#endif
+}

@@ -1,10 +1,57 @@
 // The library's second translation unit: every kernel compiled with a
 // material set (MATS != kMatsNone), reached through frt_mats::pick /
-// frt_mats::mlt (frt_render.hip "launch plans").  Built with the basic SGPR
-// register allocator (Makefile, MATSFLAGS); see DESIGN.md "Register-cap hazard".
-#define FRT_TU_MATS 1
+// frt_mats::mlt (frt_plans.hpp).  Built with the basic SGPR register
+// allocator (Makefile, MATSFLAGS); see DESIGN.md "Register-cap hazard".
 #undef FRT_DIAG
-#ifndef FRT_RENDER_SRC
-#define FRT_RENDER_SRC "frt_render.hip"
-#endif
-#include FRT_RENDER_SRC
+#include "frt_kernels.hpp"
+#include "frt_plans.hpp"
+
+// a context with an environment image: two material sets carry the lookup --
+// textures alone (lambertian and textured scenes) and every material
+static int pick_env(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L)
+{
+    if (integrator == FRT_INTEGRATOR_AO) return pick_launcher_kind<FRT_INTEGRATOR_AO, kMatsAll | kMatsEnv>(c, flags, L);
+    if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsEnv>(c, flags, L);
+    if (f64) return pick_launcher_f64_t<kMatsAll | kMatsEnv>(c, L);
+    if ((c->mats & ~kMatsTex) == 0) return pick_launcher_t<kMatsTex | kMatsEnv>(c, flags, L);
+    return pick_launcher_t<kMatsAll | kMatsEnv>(c, flags, L);
+}
+int frt_mats::pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L)
+{
+    if (c->env_texels) return pick_env(c, integrator, flags, f64, L);
+    if (integrator == FRT_INTEGRATOR_AO) return pick_launcher_kind<FRT_INTEGRATOR_AO, kMatsAll>(c, flags, L);
+    if (f64) {
+        switch (c->mats) {   // (a lambertian scene comes here with a BVH world only: the kMatsAll kernels)
+        case kMatsTex: return pick_launcher_f64_t<kMatsTex>(c, L);
+        case kMatsSpec: return pick_launcher_f64_t<kMatsSpec>(c, L);   // veach_mis (C3): phong plates
+        case kMatsSpec | kMatsTex: return pick_launcher_f64_t<kMatsSpec | kMatsTex>(c, L);
+        default: return pick_launcher_f64_t<kMatsAll>(c, L);
+        }
+    }
+    switch (c->mats) {   // the smallest kernel covering the scene's materials
+    case kMatsTex: return pick_launcher_t<kMatsTex>(c, flags, L);
+    case kMatsSpec:
+    case kMatsSpec | kMatsTex: return pick_launcher_t<kMatsSpec | kMatsTex>(c, flags, L);
+    default: return pick_launcher_t<kMatsAll>(c, flags, L);
+    }
+}
+template <bool MATS, bool ENV>
+static int mlt_pick(int stack, int world, bool lds, const void **boot, const void **chains)
+{
+    if (world == FRT_WORLD_LIST) mlt_kernels_t<16, FRT_WORLD_LIST, false, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh4) mlt_kernels_t<kBvh4LdsStack, kWorldBvh4, false, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh2Oct && stack == 8) mlt_kernels_t<8, kWorldBvh2Oct, true, MATS, ENV>(boot, chains);
+    else if (world == kWorldBvh2Oct && stack == 16) mlt_kernels_t<16, kWorldBvh2Oct, true, MATS, ENV>(boot, chains);
+    else if (lds && stack == 8) mlt_kernels_t<8, FRT_WORLD_BVH, true, MATS, ENV>(boot, chains);
+    else if (lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, true, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 16) mlt_kernels_t<16, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 32) mlt_kernels_t<32, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
+    else if (!lds && stack == 64) mlt_kernels_t<64, FRT_WORLD_BVH, false, MATS, ENV>(boot, chains);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+}
+// (an environment image always takes the material branch: one chain kernel per plan carries the lookup)
+int frt_mats::mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains)
+{
+    return env ? mlt_pick<true, true>(stack, world, lds, boot, chains) : mlt_pick<true, false>(stack, world, lds, boot, chains);
+}

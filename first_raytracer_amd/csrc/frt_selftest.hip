@@ -1,0 +1,135 @@
+// frt_selftest.hip -- the host self-test hooks of the C-ABI (CPU-only unit
+// tests): frt_path.hpp / frt_mlt.hpp, the code the kernels run per lane, on the
+// host over the flattened scene.  No kernel.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "frt_ctx.hpp"
+#include "frt_flatten.hpp"
+
+using namespace frt;
+
+constexpr int kSelftestStack = 8;   // small, so the host self-test exercises the overflow entries
+
+// the self-test's per-pixel loop in precision R (fp64: the binary tree or the list)
+template <typename R, int MATS = kMatsAll>
+static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_render_params *p, const int32_t *pixels,
+                            int npix, bool wide, std::vector<int> &stack, float *out_rgb, uint64_t cnt[3])
+{
+    uint32_t n_ext = 0, n_sh = 0;
+    for (int i = 0; i < npix; ++i) {
+        const int pix = pixels[i];
+        const int px = pix % p->nx, py = pix / p->nx;
+        V3<R> acc = zero3<R>();
+        for (int smp = 0; smp < p->spp; ++smp) {
+            PathState<R> P;
+            path_begin(P, S, px, py, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)(smp + p->sample_offset));
+            ++cnt[0];
+            for (;;) {
+                Hit<R> h;
+                if (S.world_kind == FRT_WORLD_LIST) {
+                    h = trace<FRT_WORLD_LIST, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+                } else if constexpr (!kIsF64<R>) {
+                    h = wide ? trace<kWorldBvh4, 1, kSelftestStack>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data())
+                             : trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+                } else {
+                    h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+                }
+                n_ext = n_sh = 0;
+                const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade<MATS>(P, S, h, n_sh)
+                                  : p->integrator == FRT_INTEGRATOR_NORMALS ? normals_shade<MATS>(P, S, h)
+                                  : path_shade<MATS>(P, S, h, p->max_depth, n_ext, n_sh);
+                cnt[1] += n_ext; cnt[2] += n_sh;
+                if (done) break;
+            }
+            acc = acc + P.L;
+        }
+        const R k = R(1) / (R)p->spp;
+        out_rgb[3 * i] = (float)(acc.x * k); out_rgb[3 * i + 1] = (float)(acc.y * k); out_rgb[3 * i + 2] = (float)(acc.z * k);
+    }
+}
+
+// Self-test hook (CPU-only unit tests): runs frt_path.hpp -- the code the
+// megakernel runs per lane -- on the host over the flattened scene, in fp32 or
+// (FRT_FLAG_FP64) in fp64.  Not a render path: frt_render / frt_render_device
+// never call it.
+extern "C" int frt_selftest_path_host(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
+                                      int npix, float *out_rgb, frt_stats *st)
+{
+    return frt_selftest_path_host_env(sv, p, pixels, npix, nullptr, out_rgb, st);
+}
+// ... with an environment image (frt_set_env_image's validation and conversion; NULL = none)
+extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
+                                          int npix, const frt_image *env, float *out_rgb, frt_stats *st)
+{
+    if (!sv || !p || !pixels || !out_rgb || npix < 0 || p->spp <= 0 || p->nx <= 0 || p->ny <= 0) return FRT_E_INVALID;
+    for (int i = 0; i < npix; ++i)
+        if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
+    const bool f64 = (p->flags & FRT_FLAG_FP64) != 0;
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, f64);
+    if (rc != FRT_OK) return rc;
+    if (p->integrator == FRT_INTEGRATOR_AO)
+        for (int i = 0; i < sv->n_materials; ++i)
+            if (sv->materials[i].type == FRT_MAT_METAL) return FRT_E_UNSUPPORTED;
+    DevScene S = host_scene(F);
+    std::vector<float4> env_tex;
+    if (env) {
+        const int erc = env_texels_of(env, env_tex, err);
+        if (erc != FRT_OK) return erc;
+        S.env_texels = env_tex.data(); S.env_nx = env->nx; S.env_ny = env->ny;
+    }
+    std::vector<int> stack(std::max(F.depth + 1, kSelftestStack));
+    const bool wide = !f64 && S.world_kind == FRT_WORLD_BVH && F.has4 && !(p->flags & FRT_FLAG_BVH2) &&
+                      bvh4_stack_fits(F.depth4, kSelftestStack);
+    uint64_t cnt[3] = {0, 0, 0};   // camera, extension, shadow
+    constexpr int kEnvAll = kMatsAll | kMatsEnv;   // with an image: the code of the kMatsEnv kernels
+    if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (env) selftest_pixels<float, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else selftest_pixels<float>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    if (st) {
+        memset(st, 0, sizeof(*st));
+        st->camera_rays = cnt[0]; st->extension_rays = cnt[1]; st->shadow_rays = cnt[2];
+        st->samples = cnt[0]; st->pixels = (uint64_t)npix;
+        st->stack_entries = wide ? (uint32_t)kSelftestStack : (uint32_t)stack.size();
+        st->bvh_depth = (uint32_t)(wide ? F.depth4 : F.depth);   // which tree was traversed
+        st->fp64 = f64 ? 1u : 0u;
+    }
+    return FRT_OK;
+}
+
+
+// Self-test hook: n PSS-MLT bootstrap eye paths (fresh primary samples from the
+// bootstrap stream) through frt_mlt.hpp on the host; out6[i] = x, y, r, g, b, sc.
+extern "C" int frt_selftest_mlt_paths_host(const frt_scene_view *sv, int nx, int ny, uint32_t seed, int n,
+                                           float *out6)
+{
+    if (!sv || !out6 || n < 0 || nx <= 0 || ny <= 0) return FRT_E_INVALID;
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false);
+    if (rc != FRT_OK) return rc;
+    const DevScene S = host_scene(F);
+    std::vector<int> stack(std::max(F.depth + 1, 1));
+    for (int i = 0; i < n; ++i) {
+        PrndSource src{nullptr, 0, 0, rng_key(seed ^ kMltBootSalt, (uint32_t)i, 0u), 0u, true, 0.0f, 0.0f};
+        MltPath M;
+        mlt_begin(M, S, src, nx, ny);
+        uint32_t ne = 0, ns = 0;
+        for (;;) {
+            if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * env_of<float>(S); break; }
+            const Hit<float> h = (S.world_kind == FRT_WORLD_LIST)
+                              ? trace<FRT_WORLD_LIST, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data())
+                              : trace<FRT_WORLD_BVH, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data());
+            if (mlt_shade(M, S, h, src, ne, ns)) break;
+        }
+        const f3 L = M.P.L;
+        float *o = &out6[6 * (size_t)i];
+        o[0] = M.x; o[1] = M.y; o[2] = L.x; o[3] = L.y; o[4] = L.z; o[5] = fmaxf(fmaxf(L.x, L.y), L.z);
+    }
+    return FRT_OK;
+}

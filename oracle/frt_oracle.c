@@ -1386,7 +1386,7 @@ double ora_mlt_bootstrap(const ora_scene *s, int nx, int ny, uint32_t seed, int 
 /* pssmlt::Render (pssmlt.cpp:301-365) for the chains of one shard: of
  * n_chains chains of `steps` mutations each, the n_local chains
  * c = shard_index + j * shard_count (j = 0, 1, ...), the GPU's shard rule
- * (frt_render.hip MltWork).  film (nx*ny*3, zeroed by the caller) receives
+ * (frt_kernels.hpp MltWork).  film (nx*ny*3, zeroed by the caller) receives
  * their splats scaled by nx*ny/(n_chains*steps) as AccumulatePathContribution
  * does with ns, so the shard films of all shards sum to the full render.
  * Per local chain j (optional): fp[2j] = accepted proposals, fp[2j+1] = the

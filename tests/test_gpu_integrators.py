@@ -1,5 +1,5 @@
 """GPU parity of the reference's other integrators, run by the same persistent
-megakernel (KIND template, csrc/frt_render.hip) through the C-ABI:
+megakernel (KIND template, csrc/frt_kernels.hpp) through the C-ABI:
 ambient occlusion (ao::Li, first_ray/ao.cpp:4-27) and shading normals
 (normals_renderer::Li, first_ray/debug_renderer.h:8-17), against the fp64
 oracle on the same counter-RNG streams.

@@ -165,7 +165,7 @@ def test_bvh4_matches_binary(ctx, cornell_obj, tmp_path):
 
 
 def test_lean_plan_rounding(ctx, cornell_obj):
-    """The HBM lambertian plans keep less per-lane state (kLean, frt_render.hip):
+    """The HBM lambertian plans keep less per-lane state (kLean, frt_kernels.hpp):
     each radiance contribution is added to the fp32 item sum as it is found,
     where the LDS plan sums a sample first.  Same rays, same hits, so the films
     agree to fp32 summation rounding -- pinned here as a tolerance, not
