@@ -33,6 +33,9 @@ struct frt_ctx {
     float4 *env_texels = nullptr;
     int env_nx = 0, env_ny = 0;
     uint64_t env_hash = 0;        // of the texels (frt_render_multi: every context must hold the same image)
+    // FRT_FLAG_ENV_SAMPLING: the image's sampling tables (csrc/host/envdist.cpp) behind the texels
+    // in env_texels, built by the first render that asks for them and kept until the image changes
+    enum { kEnvTabNone, kEnvTabBuilt, kEnvTabDark } env_tab = kEnvTabNone;   // Dark: no luminance, not sampled
     bool has_metal = false;       // ao::Li cannot sample metal (constant_pdf::generate throws, pdf.h:195-198)
     size_t scene_lds_bytes = 0;                         // LDS copy with the binary nodes
     size_t scene_lds_bytes_oct = 0;                     // ... with the 8 octant copies of the binary nodes

@@ -731,6 +731,10 @@ FRT_HD V3<R> prim_sample(const DevScene &S, int ref, V3<R> o, R u0, R u1, V3<R> 
 // kernels hold no trace of the lookup.
 constexpr int kMatsNone = 0, kMatsTex = 1, kMatsSpec = 2, kMatsRough = 4, kMatsAll = 7;
 constexpr int kMatsEnv = 8;
+// kMatsEnvNee (with kMatsEnv): the path integrator also samples the image --
+// next-event estimation toward it, MIS with the bsdf sample (FRT_FLAG_ENV_SAMPLING;
+// env_sample, path_shade).  Only renders with that flag run these kernels.
+constexpr int kMatsEnvNee = 16;
 constexpr int kMatsSpecAny = kMatsSpec | kMatsRough;
 
 // ---- textures (texture.h:30-49), MATS kernels only ----
@@ -793,7 +797,7 @@ template <typename R> FRT_HD f3 image_texel(const DevScene &S, float4 m4, R tu, 
 // fp32 only: normalize() can leave |d.y| an ulp above 1, where acosf gives NaN
 // and x86_trunc an arbitrary row; d.y is clamped to [-1, 1] there (the pole's
 // row).  The fp64 kernels follow the reference to the letter.
-template <typename R> FRT_HD V3<R> env_eval(const DevScene &S, V3<R> rd)
+template <typename R> FRT_HD int env_index(const DevScene &S, V3<R> rd)   // the texel a direction reads
 {
     const V3<R> d = normalize(rd);
     R dy = d.y;
@@ -802,8 +806,84 @@ template <typename R> FRT_HD V3<R> env_eval(const DevScene &S, V3<R> rd)
     if (phi < R(0)) phi = phi + Cst<R>::pi * R(2);
     if (theta < R(0)) theta = theta + Cst<R>::pi;
     const R u = phi / (R(2) * Cst<R>::pi), v = theta / Cst<R>::pi;
-    const f3 c = xyz(S.env_texels[image_index(S.env_nx, S.env_ny, u, v)]);
+    return image_index(S.env_nx, S.env_ny, u, v);
+}
+template <typename R> FRT_HD V3<R> env_texel(const DevScene &S, int k)
+{
+    const f3 c = xyz(S.env_texels[k]);
     return V3<R>{R(c.x), R(c.y), R(c.z)};
+}
+template <typename R> FRT_HD V3<R> env_eval(const DevScene &S, V3<R> rd) { return env_texel<R>(S, env_index(S, rd)); }
+
+// ---- sampling the environment image (FRT_FLAG_ENV_SAMPLING; kMatsEnvNee kernels) ----
+// The tables of csrc/host/envdist.cpp follow the texels in their buffer: the
+// marginal CDF over rows (ny + 1 floats), then a conditional CDF per row (nx + 1
+// each).  A texel's probability is the product of the two table differences;
+// its density over directions is that over the row's texel solid angle.
+// The search is a chain of at most log2(ny) + log2(nx) dependent loads from
+// tables that stay in the vector L1 / L2 (one row's conditional is contiguous);
+// lanes of a wave search different rows, so there is nothing wave-uniform to
+// keep in scalar registers or LDS.
+FRT_HD const float *env_marginal(const DevScene &S)
+{
+    return reinterpret_cast<const float *>(S.env_texels + (size_t)S.env_nx * (size_t)S.env_ny);
+}
+FRT_HD const float *env_conditional(const DevScene &S, int j)
+{
+    return env_marginal(S) + (S.env_ny + 1) + (size_t)j * (size_t)(S.env_nx + 1);
+}
+// largest k in [0, n) with cdf[k] <= u (cdf[0] = 0 <= u < 1 = cdf[n]: the interval found is not empty)
+template <typename R> FRT_HD int env_cdf_find(const float *cdf, int n, R u)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (R(cdf[mid]) <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// row j spans cos(theta) in [c0 - dc, c0]; dc as a product (no cancellation at the poles)
+template <typename R> FRT_HD R env_row_dcos(const DevScene &S, int j, R &c0)
+{
+    const R half = Cst<R>::pi / (R)(2 * S.env_ny);
+    c0 = vcos((R)(2 * j) * half);
+    return R(2) * vsin((R)(2 * j + 1) * half) * vsin(half);
+}
+// density over solid angle inside a texel of probability `prob` in a row spanning dc
+template <typename R> FRT_HD R env_density(const DevScene &S, R prob, R dc)
+{
+    return fdiv(prob * (R)S.env_nx, R(2) * Cst<R>::pi * dc);
+}
+template <typename R> struct EnvSample { V3<R> d, E; R pdf; };
+// u0 picks the row, u1 the column; their rescaled remainders place the direction
+// inside the texel, uniform in solid angle.  d inverts env_index's (phi, theta).
+template <typename R> FRT_HD EnvSample<R> env_sample(const DevScene &S, R u0, R u1)
+{
+    const R below_one = R(0x1.fffffep-1f);
+    u0 = vmin(u0, below_one); u1 = vmin(u1, below_one);
+    const float *marg = env_marginal(S);
+    const int j = env_cdf_find(marg, S.env_ny, u0);
+    const float *cond = env_conditional(S, j);
+    const int i = env_cdf_find(cond, S.env_nx, u1);
+    const R m0 = R(marg[j]), pm = R(marg[j + 1]) - m0, q0 = R(cond[i]), pq = R(cond[i + 1]) - q0;
+    const R t0 = vmin(fdiv(u0 - m0, pm), below_one), t1 = vmin(fdiv(u1 - q0, pq), below_one);
+    R c0;
+    const R dc = env_row_dcos(S, j, c0);
+    const R ct = vmin(vmax(c0 - t0 * dc, R(-1)), R(1)), st = fsqrt(vmax(R(1) - ct * ct, R(0)));
+    const R phi = R(2) * Cst<R>::pi * fdiv((R)i + t1, (R)S.env_nx);
+    EnvSample<R> e;
+    e.d = V3<R>{st * vsin(phi), ct, -st * vcos(phi)};
+    e.E = env_texel<R>(S, j * S.env_nx + i);
+    e.pdf = env_density(S, pm * pq, dc);
+    return e;
+}
+// the same density for the direction of a ray that left the scene: of the texel env_eval reads
+template <typename R> FRT_HD R env_pdf(const DevScene &S, int k)
+{
+    const int j = k / S.env_nx, i = k - j * S.env_nx;
+    const float *m = env_marginal(S) + j, *q = env_conditional(S, j) + i;
+    R c0;
+    return env_density(S, (R(m[1]) - R(m[0])) * (R(q[1]) - R(q[0])), env_row_dcos(S, j, c0));
 }
 // Scene::env_map->eval for the ray direction rd that left the scene: the image
 // in kernels compiled with kMatsEnv (a context with an environment image runs
@@ -979,6 +1059,7 @@ FRT_HD bool mat_no_mis(int t) { return t == FRT_MAT_MODIFIED_PHONG || t == FRT_M
 template <int MATS = kMatsAll, typename R>
 FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
+    constexpr bool kEnvNee = (MATS & kMatsEnvNee) != 0;
     if (P.shadow) {
         if (!path_after_shadow<MATS>(P, h.prim < 0)) return true;
         ++n_ext;
@@ -986,6 +1067,13 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     }
     if (P.term) return true;                            // finished in the traversal loop
     if (h.prim < 0) {                                   // path.cpp:115 environment
+        if constexpr (kEnvNee) {                        // the previous vertex also sampled the image: MIS, as a light hit
+            if (P.depth != 0 && !P.prev_spec) {
+                const int k = env_index(S, P.rd);
+                P.L = P.L + mi_weight(P.prev_pdf, env_pdf<R>(S, k)) * (P.beta * env_texel<R>(S, k));
+                return true;
+            }
+        }
         P.L = P.L + P.beta * env_radiance<MATS>(S, P.rd);
         return true;
     }
@@ -1041,9 +1129,25 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     // dot(n, wo); the constant lets the compiler drop the state.
     // NEE's light pick (path.cpp:39-40)
     const int nl = S.n_lights;
-    int idx = (int)(rng_r<R>(P.key, base + 3) * (R)nl);
+    R pick = rng_r<R>(P.key, base + 3);
+    // kEnvNee: a lambertian or rough conductor vertex -- the ones whose next hit is
+    // MIS-weighted -- samples the image instead, always in a scene without lights,
+    // else with probability 1/2; the rescaled remainder then feeds the reference's
+    // pick.  inv_sel = 1 / the probability of the strategy taken.
+    bool env_pick = false;
+    R inv_sel = R(1);
+    if constexpr (kEnvNee) {
+        if (lamb || mtype == FRT_MAT_ROUGH_CONDUCTOR) {
+            env_pick = nl == 0 || pick < R(0.5f);
+            if (nl != 0) {
+                inv_sel = R(2);
+                pick = env_pick ? pick * R(2) : pick * R(2) - R(1);
+            }
+        }
+    }
+    int idx = (int)(pick * (R)nl);
     if (idx == nl) idx -= 1;
-    const bool nee = idx >= 0 && !diel;
+    const bool nee = (idx >= 0 && !diel) || env_pick;
     P.term = (MATS & kMatsSpecAny) && pdf == R(0);
     if (P.term && !nee) return true;
     // origin of the next ray: off the surface on the side it leaves (path.cpp:91-93, 99)
@@ -1052,7 +1156,23 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     P.nxt_d = wo;
     if constexpr ((MATS & kMatsSpecAny) != 0) P.nxt_o = origin;
     // next-event estimation (path.cpp:38-77); not from dielectrics (path.cpp:40)
-    if (nee) {
+    if (kEnvNee && env_pick) {
+        // toward the drawn texel: its radiance and density, the bsdf terms of the
+        // area-light branch below; a lambertian vertex takes no light from under
+        // its shading normal (its bsdf sample never goes there)
+        const EnvSample<R> e = env_sample(S, rng_r<R>(P.key, base + 4), rng_r<R>(P.key, base + 5));
+        const R cos_wi = dot(n, e.d);
+        const bool l = !(MATS & kMatsSpecAny) || lamb;
+        P.nee = zero3<R>();
+        if (e.pdf > R(0) && !(l && cos_wi <= R(0))) {
+            const V3<R> f = l ? cos_wi * (Cst<R>::inv_pi * rgb<R>(m0)) : spec_eval<MATS>(M, n, wi, e.d);
+            const R bsdf_pdf = l ? cos_wi * Cst<R>::inv_pi : spec_value<MATS>(M, n, wi, e.d);
+            P.nee = (inv_sel * fdiv(mi_weight(e.pdf, bsdf_pdf), e.pdf)) * (P.beta * (e.E * f));
+        }
+        P.ro = nee_o; P.rd = e.d; P.rtmax = Cst<R>::tmax;
+        P.shadow = true;
+        ++n_sh;
+    } else if (nee) {
         const int lref = S.lights[idx];
         V3<R> ln;
         int lmat;
@@ -1073,6 +1193,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
             if (f2i(lm0.w) == FRT_MAT_DIFFUSE_LIGHT && dot(ln, tu) < R(0))
                 P.nee = fdiv(wgt, light_pdf) * (P.beta * (rgb<R>(lm1) * f));
         }
+        if constexpr (kEnvNee) P.nee = inv_sel * P.nee;
         P.ro = nee_o; P.rd = tl; P.rtmax = R(1) - Cst<R>::shadow_eps;
         P.shadow = true;
         ++n_sh;

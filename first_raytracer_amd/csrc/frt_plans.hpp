@@ -218,6 +218,8 @@ namespace frt_mats {
 // the scene's material set c->mats (!= kMatsNone); and every integrator of a
 // context with an environment image (the kMatsEnv kernels)
 int pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L);
+// the path kernels that also sample the environment image (FRT_FLAG_ENV_SAMPLING)
+int pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher &L);
 // PSS-MLT with the material branch or (env) the environment image, for the
 // (stack, world, lds) plans of render_mlt
 int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);

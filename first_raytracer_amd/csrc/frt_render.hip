@@ -15,6 +15,7 @@
 #include "frt_plans.hpp"
 #include "frt_flatten.hpp"
 #include "frt_lbvh.hpp"
+#include "host/envdist.hpp"
 
 namespace {
 
@@ -197,6 +198,8 @@ static int upload_vec(frt_ctx *c, const std::vector<T> &v, P *dst)
 // copy is not touched); renders after this call run the kernels compiled with
 // the lookup (kMatsEnv: frt_mats::pick, frt_mats::mlt), NULL returns to the
 // uploaded view's env_color and to the kernels the scene ran before.
+// The buffer has room behind the texels for the sampling tables of
+// FRT_FLAG_ENV_SAMPLING (env_tables): a new image starts without them.
 extern "C" int frt_set_env_image(frt_ctx *c, const frt_image *img)
 {
     if (!c) return FRT_E_INVALID;
@@ -209,7 +212,7 @@ extern "C" int frt_set_env_image(frt_ctx *c, const frt_image *img)
         std::string err;
         const int rc = env_texels_of(img, tex, err);
         if (rc != FRT_OK) return set_err(c, rc, err);
-        HIPCHK(c, hipMalloc((void **)&dev, tex.size() * sizeof(float4)));
+        HIPCHK(c, hipMalloc((void **)&dev, (tex.size() + env_table_records(img->nx, img->ny)) * sizeof(float4)));
         if (hipMemcpy(dev, tex.data(), tex.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipFree(dev);
             return set_err(c, FRT_E_HIP, "frt_set_env_image: copy to the device failed");
@@ -222,7 +225,24 @@ extern "C" int frt_set_env_image(frt_ctx *c, const frt_image *img)
     HIPCHK(c, hipStreamSynchronize(c->stream));   // no render of this context still reads the old buffer
     if (c->env_texels) (void)hipFree(c->env_texels);
     c->env_texels = dev; c->env_nx = nx; c->env_ny = ny; c->env_hash = hash;
+    c->env_tab = frt_ctx::kEnvTabNone;
     c->S.env_texels = dev; c->S.env_nx = nx; c->S.env_ny = ny;
+    return FRT_OK;
+}
+
+// FRT_FLAG_ENV_SAMPLING: the context's image has its sampling tables behind the
+// texels.  Built here, on the host from the texels the kernels read, at the first
+// render that wants them; no render in flight reads that part of the buffer.
+static int env_tables(frt_ctx *c)
+{
+    if (c->env_tab != frt_ctx::kEnvTabNone) return FRT_OK;
+    const size_t n = (size_t)c->env_nx * c->env_ny;
+    std::vector<float4> tex(n);
+    HIPCHK(c, hipMemcpy(tex.data(), c->env_texels, n * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<float> tab;
+    const bool lit = env_tables_of(&tex[0].x, c->env_nx, c->env_ny, tab);
+    HIPCHK(c, hipMemcpy(c->env_texels + n, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->env_tab = lit ? frt_ctx::kEnvTabBuilt : frt_ctx::kEnvTabDark;
     return FRT_OK;
 }
 
@@ -344,9 +364,10 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
     if (p->flags & FRT_FLAG_FP64) return true;
     return c->precision == FRT_PRECISION_FP64 || (c->precision == FRT_PRECISION_AUTO && c->world_kind == FRT_WORLD_LIST);
 }
-static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64)
+static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64, bool env_sampling)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
+    if (env_sampling) return frt_mats::pick_env_sampling(c, flags, f64, L);   // the kMatsEnvNee kernels
     if (c->env_texels) return frt_mats::pick(c, integrator, flags, f64, L);   // the kMatsEnv kernels
     if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsNone>(c, flags, L);
     if (integrator == FRT_INTEGRATOR_AO || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
@@ -725,7 +746,18 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
     HIPCHK(c, hipSetDevice(c->device));
     c->mlt_rows = 0;                                   // `partial` is about to be reused
-    if (p->integrator == FRT_INTEGRATOR_PSSMLT) return render_mlt(c, p, dev_slots, st, stats);
+    if (p->integrator == FRT_INTEGRATOR_PSSMLT) {
+        if (p->flags & FRT_FLAG_ENV_SAMPLING)
+            return set_err(c, FRT_E_INVALID, "FRT_FLAG_ENV_SAMPLING: pssmlt does not sample the environment image "
+                                             "(its primary-sample layout is the reference's); render without the flag");
+        return render_mlt(c, p, dev_slots, st, stats);
+    }
+    // FRT_FLAG_ENV_SAMPLING: path renders of a context with an image that has any luminance
+    bool env_sampling = false;
+    if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator == FRT_INTEGRATOR_PATH && c->env_texels) {
+        if (const int trc = env_tables(c)) return trc;
+        env_sampling = c->env_tab == frt_ctx::kEnvTabBuilt;
+    }
     if (p->integrator == FRT_INTEGRATOR_AO && c->has_metal)   // ao::Li -> constant_pdf::generate throws (pdf.h:195-198)
         return set_err(c, FRT_E_UNSUPPORTED, "ao integrator: metal has no sampling pdf (constant_pdf::generate)");
     const int T = eff_tile(p);
@@ -738,7 +770,7 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     // kernel variant: stack depth, world kind, LDS-resident scene
     Launcher L;
     const bool f64 = use_f64(c, p);
-    const int prc = pick_launcher(c, p->integrator, p->flags, L, f64);
+    const int prc = pick_launcher(c, p->integrator, p->flags, L, f64, env_sampling);
     if (prc == FRT_E_INVALID)
         return set_err(c, prc, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
                                "before frt_upload_scene");

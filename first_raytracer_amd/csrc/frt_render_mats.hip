@@ -35,6 +35,51 @@ int frt_mats::pick(const frt_ctx *c, int integrator, int flags, bool f64, Launch
     default: return pick_launcher_t<kMatsAll>(c, flags, L);
     }
 }
+// Path renders with FRT_FLAG_ENV_SAMPLING on a context with an environment image
+// (the kMatsEnvNee kernels): one material set, every material, and one register
+// cap per residency -- the specular sets' defaults, 4 waves from LDS and 5 from
+// HBM -- so the FRT_FLAG_WAVES* A/B flags and FRT_MATS_WAVES do not apply here.
+// Every residency a context can have is covered: the flag never falls back to a
+// kernel without the sampling.
+constexpr int kMatsNee = kMatsAll | kMatsEnv | kMatsEnvNee;
+static int pick_launcher_nee(const frt_ctx *c, int flags, Launcher &L)
+{
+    if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, kMatsNee>(0); return FRT_OK; }
+    const int d = c->stack_needed;
+    const size_t sb = c->scene_lds_bytes;
+    const auto [lds, oct, wide] = residency(c, flags);
+    if (oct) {
+        L = d < 8 ? make_launcher<8, kWorldBvh2Oct, true, 4, kMatsNee>(c->scene_lds_bytes_oct)
+                  : make_launcher<16, kWorldBvh2Oct, true, 4, kMatsNee>(c->scene_lds_bytes_oct);
+    } else if (lds) {
+        L = d < 8 ? make_launcher<8, FRT_WORLD_BVH, true, 4, kMatsNee>(sb)
+                  : make_launcher<16, FRT_WORLD_BVH, true, 4, kMatsNee>(sb);
+    } else if (wide) {
+        L = make_launcher<kBvh4LdsStack, kWorldBvh4, false, 5, kMatsNee>(0);
+    } else if (d < 16) {
+        L = make_launcher<16, FRT_WORLD_BVH, false, 5, kMatsNee>(0);
+    } else if (d < 32) {
+        L = make_launcher<32, FRT_WORLD_BVH, false, 5, kMatsNee>(0);
+    } else if (d < 64) {
+        L = make_launcher<64, FRT_WORLD_BVH, false, 1, kMatsNee>(0);
+    } else {
+        return FRT_E_UNSUPPORTED;
+    }
+    return FRT_OK;
+}
+static int pick_launcher_nee_f64(const frt_ctx *c, Launcher &L)
+{
+    if (c->world_kind == FRT_WORLD_LIST)
+        L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsNee, FRT_INTEGRATOR_PATH, double>(0);
+    else if (c->stack_needed < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, kMatsNee, FRT_INTEGRATOR_PATH, double>(0);
+    else if (c->stack_needed < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, kMatsNee, FRT_INTEGRATOR_PATH, double>(0);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+}
+int frt_mats::pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher &L)
+{
+    return f64 ? pick_launcher_nee_f64(c, L) : pick_launcher_nee(c, flags, L);
+}
 template <bool MATS, bool ENV>
 static int mlt_pick(int stack, int world, bool lds, const void **boot, const void **chains)
 {

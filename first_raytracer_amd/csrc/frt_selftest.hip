@@ -8,6 +8,7 @@
 
 #include "frt_ctx.hpp"
 #include "frt_flatten.hpp"
+#include "host/envdist.hpp"
 
 using namespace frt;
 
@@ -77,9 +78,19 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
             if (sv->materials[i].type == FRT_MAT_METAL) return FRT_E_UNSUPPORTED;
     DevScene S = host_scene(F);
     std::vector<float4> env_tex;
+    bool env_sampling = false;
     if (env) {
         const int erc = env_texels_of(env, env_tex, err);
         if (erc != FRT_OK) return erc;
+        // FRT_FLAG_ENV_SAMPLING: the tables behind the texels, as on a context
+        if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator != FRT_INTEGRATOR_AO &&
+            p->integrator != FRT_INTEGRATOR_NORMALS) {
+            std::vector<float> tab;
+            env_sampling = env_tables_of(&env_tex[0].x, env->nx, env->ny, tab);
+            const size_t n = env_tex.size();
+            env_tex.resize(n + tab.size() / 4);
+            memcpy(reinterpret_cast<float *>(env_tex.data() + n), tab.data(), tab.size() * sizeof(float));
+        }
         S.env_texels = env_tex.data(); S.env_nx = env->nx; S.env_ny = env->ny;
     }
     std::vector<int> stack(std::max(F.depth + 1, kSelftestStack));
@@ -87,7 +98,10 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
                       bvh4_stack_fits(F.depth4, kSelftestStack);
     uint64_t cnt[3] = {0, 0, 0};   // camera, extension, shadow
     constexpr int kEnvAll = kMatsAll | kMatsEnv;   // with an image: the code of the kMatsEnv kernels
-    if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    constexpr int kEnvNee = kEnvAll | kMatsEnvNee;   // ... and of the kernels that sample it
+    if (f64 && env_sampling) selftest_pixels<double, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (env_sampling) selftest_pixels<float, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else if (env) selftest_pixels<float, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else selftest_pixels<float>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);

@@ -4,13 +4,17 @@
 //
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
 //              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals] [--chains 262144]
-//              [--env r,g,b | --env-map file.hdr] [--out out.pfm] [--png out.png] [--bvh reference|sah]
+//              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
 // --env: constant environment colour (the reference scenes' is black).
 // --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
 //   image_texture, material.h:206-244); exclusive with --env.
+// --env-sampling: path also samples that image at diffuse and rough vertices
+//   (FRT_FLAG_ENV_SAMPLING: the same expectation, far less noise under a sun or a
+//   window); needs --env-map, and the path integrator (ao / normals have no light
+//   sampling, pssmlt keeps the reference's sample layout).
 // --png: also the tonemapped display image (viewer::add_sample bytes, image::save_image).
 // --bvh sah: rebuild the scene's BVH with the binned SAH builder (faster traversal;
 //   exact-t ties then follow that tree's order instead of create_bvh's).
@@ -28,7 +32,7 @@ int main(int argc, char **argv)
     long ns = 100;
     unsigned seed = 0;
     double env[3] = {0, 0, 0};
-    bool has_env = false;
+    bool has_env = false, env_sampling = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -51,10 +55,16 @@ int main(int argc, char **argv)
             has_env = true;
         }
         else if (a == "--env-map") env_map = next();
+        else if (a == "--env-sampling") env_sampling = true;
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
     if (has_env && !env_map.empty()) { std::fprintf(stderr, "--env and --env-map exclude each other\n"); return 2; }
+    if (env_sampling && env_map.empty()) { std::fprintf(stderr, "--env-sampling needs --env-map\n"); return 2; }
+    if (env_sampling && integrator != "path") {
+        std::fprintf(stderr, "--env-sampling: only --integrator path samples the environment image\n");
+        return 2;
+    }
     try {
         std::printf("Resolution: %dx%d\nSetting number of samples to %ld\n", nx, ny, ns);
         const std::string kind = scene == "cornell" ? "cornell_box_obj" : scene == "veach" ? "veach_mis" : "obj_smooth";
@@ -78,6 +88,7 @@ int main(int argc, char **argv)
             run(render);
         } else if (integrator == "path") {
             frt::renderer<frt::path_gpu> render;
+            render.env_sampling = env_sampling;
             run(render);
         } else if (integrator == "ao") {
             frt::renderer<frt::ao_gpu> render;

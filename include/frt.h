@@ -60,7 +60,34 @@ enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes
           speculative traversal), measured slower and removed in round 4; FRT_E_INVALID since round 5 */
        FRT_FLAG_NO_OCT = 256,          /* LDS binary plan without the per-octant node copies (A/B timing) */
        FRT_FLAG_FP64 = 512,            /* path: the fp64 kernel for this call (self-test: fp64 host replay) */
-       FRT_FLAG_FP32 = 1024 };         /* path: the fp32 kernels even where the precision picks fp64      */
+       FRT_FLAG_FP32 = 1024,           /* path: the fp32 kernels even where the precision picks fp64      */
+       FRT_FLAG_ENV_SAMPLING = 2048 }; /* path: next-event estimation toward the environment image, MIS with the bsdf sample */
+
+/* FRT_FLAG_ENV_SAMPLING (frt_render, frt_render_device, frt_render_multi and
+ * frt_selftest_path_host_env; fp32 and fp64).  Not the reference's estimator --
+ * its environment_map is only evaluated where a bsdf-sampled ray leaves the
+ * scene -- but one with the same expectation and far less noise under images
+ * that hold most of their energy in a few texels (a sun, a window).
+ *   path, the context (or the replay call) holds an image: texels are drawn
+ *     with probability proportional to Rec.709 luminance x the texel's solid
+ *     angle, from tables built once per image on the host (at the first such
+ *     render, kept until frt_set_env_image changes or clears the image).  At a
+ *     lambertian or rough conductor vertex the image is sampled instead of an
+ *     area light: always when the scene has no lights, else with probability
+ *     1/2 (the light-pick sample decides; its remainder feeds the reference's
+ *     pick and the area-light term is doubled).  One shadow ray per vertex as
+ *     before, counted in shadow_rays; the sample and the bsdf-sampled ray that
+ *     leaves the scene are combined with the power heuristic, as area lights
+ *     are.  A lambertian vertex takes nothing from below its shading normal.
+ *     Other vertices (modified_phong, metal, dielectric) are unchanged, and so
+ *     is the environment seen by the camera or after them.
+ *     The A/B register-cap flags (FRT_FLAG_WAVES4/5/6) do not apply: these
+ *     kernels have one cap per plan.
+ *   no image (constant env_color), or an image without luminance: no effect,
+ *     the film is that of the same call without the flag.
+ *   ao, normals: no effect.
+ *   pssmlt: FRT_E_INVALID with a text in frt_last_error (its primary-sample
+ *     layout is the reference's). */
 
 /* Kernel precision (frt_set_precision).  The reference computes in fp64
  * (geometry.h:351).  FRT_PRECISION_AUTO: fp64 for list worlds (hitable_list,

@@ -209,6 +209,10 @@ struct tile_gpu {
     uint32_t seed = 0;
     int max_depth = 33;     // path.cpp:36
     int tile_size = 32;
+    // path with an environment image (Scene::set_env_map): also sample the image at every
+    // diffuse or rough vertex (FRT_FLAG_ENV_SAMPLING, frt.h) -- not the reference's estimator,
+    // the same expectation with far less noise under a sun or a window; off by default
+    bool env_sampling = false;
     frt_stats last_stats{};
     static constexpr bool using_custom_viewer = false;
 
@@ -219,6 +223,7 @@ struct tile_gpu {
         p.nx = film->nx; p.ny = film->ny; p.spp = (int)film->ns; p.seed = seed;
         p.max_depth = max_depth; p.integrator = INTEGRATOR; p.tile_size = tile_size;
         p.shard_index = 0; p.shard_count = 1;
+        if (env_sampling) p.flags |= FRT_FLAG_ENV_SAMPLING;
         std::vector<float> rgb((size_t)film->nx * film->ny * 3, 0.0f);
         check(frt_render_multi(gpus.data(), gpus.size(), &p, rgb.data(), &last_stats), "frt_render_multi",
               gpus.data()[0]);

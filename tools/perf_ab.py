@@ -4,7 +4,7 @@
 kernel ms and Grays/s as JSON lines.
 
   python tools/perf_ab.py [--scene cornell|cornell_1m|veach] [--spp 64] [--rounds 5]
-                          [--variants default,waves5,default/leaf1]
+                          [--variants default,waves5,default/leaf1] [--env-image 32x16]
 
 A variant is FLAG[+FLAG...][/leafN][/travN][/descN][/grabN][/sptN][/spiN]: render flags (travN sets
 FRT_TRAV_MIN=N, descN FRT_MIN_DESC=N for its renders), on a scene uploaded with
@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--chains", type=int, default=1 << 18)
     ap.add_argument("--save-films", default="", help="npz of each variant's last film (cross-library checks)")
     ap.add_argument("--env", default="", help="constant environment r,g,b (AO: 1,1,1 unless given)")
+    ap.add_argument("--env-image", default="", help="NXxNY: a synthetic environment image on every context "
+                    "(0.25 everywhere, one texel at 3000, 2000, 1000); the env_sampling variant samples it")
     args = ap.parse_args()
     import numpy as np
     import torch  # noqa: F401  (single HIP runtime)
@@ -48,6 +50,8 @@ def main():
     names = {"default": 0, "no_lds": frt.FRT_FLAG_NO_LDS_SCENE, "waves4": frt.FRT_FLAG_WAVES4,
              "waves5": frt.FRT_FLAG_WAVES5, "waves6": frt.FRT_FLAG_WAVES6, "bvh2": frt.FRT_FLAG_BVH2,
              "no_oct": frt.FRT_FLAG_NO_OCT, "fp32": frt.FRT_FLAG_FP32}
+    if hasattr(frt, "FRT_FLAG_ENV_SAMPLING"):   # (an older revision under FRT_PKG_ROOT has none: the variant is skipped)
+        names["env_sampling"] = frt.FRT_FLAG_ENV_SAMPLING
     flags = {}
     for v in args.variants.split(","):
         parts = v.split("/")[0].split("+")
@@ -84,6 +88,11 @@ def main():
                 os.environ.pop("FRT_LEAF_SIZE", None)
             ctxs[leaf] = frt.Context(0)
             ctxs[leaf].upload(hs)
+            if args.env_image:
+                ex, ey = (int(v) for v in args.env_image.split("x"))
+                image = np.full((ey, ex, 3), 0.25, np.float32)
+                image[ey // 5, ex // 6] = (3000.0, 2000.0, 1000.0)
+                ctxs[leaf].set_env_image(image)
     os.environ.pop("FRT_LEAF_SIZE", None)
     res = {v: [] for v in chosen}
     rays = {}
