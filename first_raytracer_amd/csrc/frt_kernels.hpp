@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
     // The flushes round each contribution into the fp32 item sum, so a lean
     // plan's film equals the per-sample plans' to fp32 rounding, not bit for
     // bit (tests/test_gpu_parity.py::test_lean_plan_rounding).
-    constexpr bool kLean = !LDS_SCENE && MATS == kMatsNone && KIND == FRT_INTEGRATOR_PATH && !kIsF64<R>;
+    constexpr bool kLean = !LDS_SCENE && (MATS & ~kMatsRoulette) == kMatsNone && KIND == FRT_INTEGRATOR_PATH && !kIsF64<R>;
     auto flush_L = [&]() {
         I.set(kIsAcc + 0, f2i(i2f(I.get(kIsAcc + 0)) + (float)P.L.x));
         I.set(kIsAcc + 1, f2i(i2f(I.get(kIsAcc + 1)) + (float)P.L.y));

@@ -735,6 +735,12 @@ constexpr int kMatsEnv = 8;
 // next-event estimation toward it, MIS with the bsdf sample (FRT_FLAG_ENV_SAMPLING;
 // env_sample, path_shade).  Only renders with that flag run these kernels.
 constexpr int kMatsEnvNee = 16;
+// kMatsRoulette: Russian roulette in the path integrator (FRT_FLAG_ROULETTE;
+// path_shade).  Only renders with that flag run these kernels; it adds no
+// material, so a lambertian scene's roulette kernel is kMatsNone | kMatsRoulette.
+constexpr int kMatsRoulette = 32;
+// the first vertex (P.depth) that plays: the vertices at depth 0, 1, 2 never do
+constexpr int kRouletteDepth = 3;
 constexpr int kMatsSpecAny = kMatsSpec | kMatsRough;
 
 // ---- textures (texture.h:30-49), MATS kernels only ----
@@ -923,7 +929,7 @@ template <typename R> struct PathState {
     V3<R> ro, rd;         // ray to trace next
     R rtmax;
     bool shadow;          // any-hit query
-    bool term;            // the path ends after this shadow ray (zero bsdf pdf)
+    bool term;            // the path ends after this shadow ray (zero bsdf pdf; kMatsRoulette: or roulette)
     V3<R> beta, L;        // throughput, radiance of this sample
     V3<R> nee;            // NEE contribution if the shadow ray is unoccluded
     V3<R> nxt_d;          // extension direction after the shadow ray
@@ -978,12 +984,19 @@ FRT_HD void path_begin(PathState<R> &P, const DevScene &S, int px, int py, int n
 // so the reference returns 0 for the vertex after tracing the shadow ray
 // (path.cpp:45-77 run before :87-90 / :103-106) -- the ray is traced and
 // counted like the reference's, its NEE term dropped.
+// kMatsRoulette: a path that lost the roulette at this vertex ends here too, and
+// keeps the vertex's NEE term (path_shade has zeroed P.nee where the pdf was 0).
 template <int MATS = kMatsAll, typename R>
 FRT_HD bool path_after_shadow(PathState<R> &P, bool unoccluded)
 {
     P.shadow = false;
-    if (P.term) return false;
-    if (unoccluded) P.L = P.L + P.nee;
+    if constexpr ((MATS & kMatsRoulette) != 0) {
+        if (unoccluded) P.L = P.L + P.nee;
+        if (P.term) return false;
+    } else {
+        if (P.term) return false;
+        if (unoccluded) P.L = P.L + P.nee;
+    }
     if constexpr ((MATS & kMatsSpecAny) != 0) P.ro = P.nxt_o;
     P.rd = P.nxt_d; P.rtmax = Cst<R>::tmax;
     ++P.depth;
@@ -1060,6 +1073,7 @@ template <int MATS = kMatsAll, typename R>
 FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
     constexpr bool kEnvNee = (MATS & kMatsEnvNee) != 0;
+    constexpr bool kRoulette = (MATS & kMatsRoulette) != 0;
     if (P.shadow) {
         if (!path_after_shadow<MATS>(P, h.prim < 0)) return true;
         ++n_ext;
@@ -1148,7 +1162,21 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     int idx = (int)(pick * (R)nl);
     if (idx == nl) idx -= 1;
     const bool nee = (idx >= 0 && !diel) || env_pick;
-    P.term = (MATS & kMatsSpecAny) && pdf == R(0);
+    const bool zero_pdf = (MATS & kMatsSpecAny) && pdf == R(0);
+    P.term = zero_pdf;
+    // Russian roulette (kMatsRoulette kernels; not in the reference): from vertex
+    // kRouletteDepth on, the path goes on with probability q = min(1, largest
+    // component of the throughput it would carry), that throughput divided by q
+    // -- the same expectation.  u is the third get3d dimension of the vertex,
+    // which nothing else reads.  A path that loses still traces this vertex's
+    // shadow ray and keeps its NEE term (P.term); a zero pdf comes first.
+    if constexpr (kRoulette) {
+        if (!zero_pdf && P.depth >= kRouletteDepth) {
+            const R q = vmin(R(1), vmax(beta_next.x, vmax(beta_next.y, beta_next.z)));
+            if (!(rng_r<R>(P.key, base + 2) < q)) P.term = true;
+            else beta_next = rcp(q) * beta_next;
+        }
+    }
     if (P.term && !nee) return true;
     // origin of the next ray: off the surface on the side it leaves (path.cpp:91-93, 99)
     const V3<R> nee_o = p + Cst<R>::eps * n;
@@ -1198,6 +1226,8 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
         P.shadow = true;
         ++n_sh;
     }
+    if constexpr (kRoulette)
+        if (zero_pdf) P.nee = zero3<R>();               // path_after_shadow adds P.nee before it looks at P.term
     P.prev_spec = (MATS & kMatsSpec) && mat_no_mis(mtype);
     P.beta = beta_next;
     P.prev_p = p;

@@ -91,6 +91,7 @@ constexpr bool kSplitLds = true;
 #endif
 namespace frt_lds {
 int path_oct(int stack, int waves, size_t scene_bytes, Launcher &L);
+int path_oct_roulette(int stack, size_t scene_bytes, Launcher &L);   // FRT_FLAG_ROULETTE: the 5-wave kernels
 int mlt_oct(int stack, const void **boot, const void **chains);
 }  // namespace frt_lds
 
@@ -205,6 +206,57 @@ static int pick_launcher_f64_t(const frt_ctx *c, Launcher &L)
     else return FRT_E_UNSUPPORTED;
     return FRT_OK;
 }
+// Path renders with FRT_FLAG_ROULETTE (the kMatsRoulette kernels): as the
+// kernels of FRT_FLAG_ENV_SAMPLING, one register cap per residency -- W_LDS,
+// W_HBM, W_WIDE, the defaults of the sibling kernels without roulette -- so the
+// FRT_FLAG_WAVES* A/B flags and FRT_MATS_WAVES do not apply.  Every residency a
+// context can have is covered: the flag never falls back to a kernel without
+// roulette.  The octant plan's lambertian kernels come from frt_lds
+// (path_oct_roulette), under that unit's scheduler flag.
+template <int MATS, int W_LDS, int W_HBM, int W_WIDE>
+static int pick_launcher_roulette_t(const frt_ctx *c, int flags, Launcher &L)
+{
+    static_assert((MATS & kMatsRoulette) != 0, "the roulette kernels' plans");
+    if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, MATS>(0); return FRT_OK; }
+    const int d = c->stack_needed;
+    const size_t sb = c->scene_lds_bytes;
+    const auto [lds, oct, wide] = residency(c, flags);
+    if (oct) {
+        if constexpr (MATS == kMatsRoulette && kSplitLds) {
+            return frt_lds::path_oct_roulette(d < 8 ? 8 : 16, c->scene_lds_bytes_oct, L);
+        } else {
+            L = d < 8 ? make_launcher<8, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct)
+                      : make_launcher<16, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct);
+        }
+    } else if (lds) {
+        L = d < 8 ? make_launcher<8, FRT_WORLD_BVH, true, W_LDS, MATS>(sb)
+                  : make_launcher<16, FRT_WORLD_BVH, true, W_LDS, MATS>(sb);
+    } else if (wide) {
+        L = make_launcher<kBvh4LdsStack, kWorldBvh4, false, W_WIDE, MATS>(0);
+    } else if (d < 16) {
+        L = make_launcher<16, FRT_WORLD_BVH, false, W_HBM, MATS>(0);
+    } else if (d < 32) {
+        L = make_launcher<32, FRT_WORLD_BVH, false, W_HBM, MATS>(0);
+    } else if (d < 64) {
+        L = make_launcher<64, FRT_WORLD_BVH, false, 1, MATS>(0);
+    } else {
+        return FRT_E_UNSUPPORTED;
+    }
+    return FRT_OK;
+}
+// ... and their fp64 kernels: the list world, or the binary tree from HBM
+// (stack 32 or 64), no register cap
+template <int MATS>
+static int pick_launcher_roulette_f64_t(const frt_ctx *c, Launcher &L)
+{
+    static_assert((MATS & kMatsRoulette) != 0, "the roulette kernels' plans");
+    if (c->world_kind == FRT_WORLD_LIST)
+        L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, MATS, FRT_INTEGRATOR_PATH, double>(0);
+    else if (c->stack_needed < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
+    else if (c->stack_needed < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+}
 template <int STACK, int WORLD, bool LDS, bool MATS, bool ENV = false>
 static void mlt_kernels_t(const void **boot, const void **chains)
 {
@@ -220,6 +272,10 @@ namespace frt_mats {
 int pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L);
 // the path kernels that also sample the environment image (FRT_FLAG_ENV_SAMPLING)
 int pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher &L);
+// the path kernels with Russian roulette (FRT_FLAG_ROULETTE) of every scene but
+// the lambertian ones without an image (those: the main unit and frt_lds);
+// env_sampling: the kernels that also sample the image
+int pick_roulette(const frt_ctx *c, int flags, bool f64, bool env_sampling, Launcher &L);
 // PSS-MLT with the material branch or (env) the environment image, for the
 // (stack, world, lds) plans of render_mlt
 int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);

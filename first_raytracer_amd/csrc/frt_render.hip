@@ -367,6 +367,16 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
 static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64, bool env_sampling)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
+    if ((flags & FRT_FLAG_ROULETTE) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsRoulette kernels
+        if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
+            return frt_mats::pick_roulette(c, flags, f64, env_sampling, L);
+        // a lambertian scene without an image: the sibling plans' caps (5 waves from LDS, 6 from HBM, 7 on the 4-wide tree)
+        if (f64) {   // a lambertian list world, as below
+            L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsRoulette, FRT_INTEGRATOR_PATH, double>(0);
+            return FRT_OK;
+        }
+        return pick_launcher_roulette_t<kMatsRoulette, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L);
+    }
     if (env_sampling) return frt_mats::pick_env_sampling(c, flags, f64, L);   // the kMatsEnvNee kernels
     if (c->env_texels) return frt_mats::pick(c, integrator, flags, f64, L);   // the kMatsEnv kernels
     if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsNone>(c, flags, L);
@@ -747,6 +757,9 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     HIPCHK(c, hipSetDevice(c->device));
     c->mlt_rows = 0;                                   // `partial` is about to be reused
     if (p->integrator == FRT_INTEGRATOR_PSSMLT) {
+        if (p->flags & FRT_FLAG_ROULETTE)
+            return set_err(c, FRT_E_INVALID, "FRT_FLAG_ROULETTE: pssmlt plays no Russian roulette "
+                                             "(its primary-sample layout is the reference's); render without the flag");
         if (p->flags & FRT_FLAG_ENV_SAMPLING)
             return set_err(c, FRT_E_INVALID, "FRT_FLAG_ENV_SAMPLING: pssmlt does not sample the environment image "
                                              "(its primary-sample layout is the reference's); render without the flag");

@@ -22,3 +22,15 @@ int frt_lds::path_oct(int stack, int waves, size_t scene_bytes, Launcher &L)
     return FRT_OK;
 #endif
 }
+// ... and with Russian roulette (FRT_FLAG_ROULETTE): one register cap, the default plan's 5 waves
+int frt_lds::path_oct_roulette(int stack, size_t scene_bytes, Launcher &L)
+{
+#if defined(FRT_OCT_IN_MAIN)
+    return FRT_E_UNSUPPORTED;
+#else
+    if (stack == 8) L = make_launcher<8, kWorldBvh2Oct, true, 5, kMatsRoulette>(scene_bytes);
+    else if (stack == 16) L = make_launcher<16, kWorldBvh2Oct, true, 5, kMatsRoulette>(scene_bytes);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+#endif
+}

@@ -80,6 +80,22 @@ int frt_mats::pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher 
 {
     return f64 ? pick_launcher_nee_f64(c, L) : pick_launcher_nee(c, flags, L);
 }
+// Path renders with FRT_FLAG_ROULETTE (the kMatsRoulette kernels): every material,
+// without an image, with one (kMatsEnv) or sampling it (kMatsEnvNee); the register
+// caps of the every-material siblings, 4 waves from LDS and 5 from HBM.
+// Lambertian and textured scenes take these supersets too (a lambertian scene
+// without an image: kMatsNone | kMatsRoulette, main unit).
+template <int MATS>
+static int pick_roulette_t(const frt_ctx *c, int flags, bool f64, Launcher &L)
+{
+    return f64 ? pick_launcher_roulette_f64_t<MATS>(c, L) : pick_launcher_roulette_t<MATS, 4, 5, 5>(c, flags, L);
+}
+int frt_mats::pick_roulette(const frt_ctx *c, int flags, bool f64, bool env_sampling, Launcher &L)
+{
+    if (env_sampling) return pick_roulette_t<kMatsNee | kMatsRoulette>(c, flags, f64, L);
+    if (c->env_texels) return pick_roulette_t<kMatsAll | kMatsEnv | kMatsRoulette>(c, flags, f64, L);
+    return pick_roulette_t<kMatsAll | kMatsRoulette>(c, flags, f64, L);
+}
 template <bool MATS, bool ENV>
 static int mlt_pick(int stack, int world, bool lds, const void **boot, const void **chains)
 {

@@ -99,7 +99,16 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
     uint64_t cnt[3] = {0, 0, 0};   // camera, extension, shadow
     constexpr int kEnvAll = kMatsAll | kMatsEnv;   // with an image: the code of the kMatsEnv kernels
     constexpr int kEnvNee = kEnvAll | kMatsEnvNee;   // ... and of the kernels that sample it
-    if (f64 && env_sampling) selftest_pixels<double, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    // FRT_FLAG_ROULETTE (path): the code of the kMatsRoulette kernels
+    constexpr int kRl = kMatsRoulette;
+    const bool roulette = (p->flags & FRT_FLAG_ROULETTE) && p->integrator == FRT_INTEGRATOR_PATH;
+    if (roulette && f64 && env_sampling) selftest_pixels<double, kEnvNee | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (roulette && env_sampling) selftest_pixels<float, kEnvNee | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (roulette && f64 && env) selftest_pixels<double, kEnvAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (roulette && f64) selftest_pixels<double, kMatsAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (roulette && env) selftest_pixels<float, kEnvAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (roulette) selftest_pixels<float, kMatsAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    else if (f64 && env_sampling) selftest_pixels<double, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else if (env_sampling) selftest_pixels<float, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
     else if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);

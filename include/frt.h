@@ -61,7 +61,8 @@ enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes
        FRT_FLAG_NO_OCT = 256,          /* LDS binary plan without the per-octant node copies (A/B timing) */
        FRT_FLAG_FP64 = 512,            /* path: the fp64 kernel for this call (self-test: fp64 host replay) */
        FRT_FLAG_FP32 = 1024,           /* path: the fp32 kernels even where the precision picks fp64      */
-       FRT_FLAG_ENV_SAMPLING = 2048 }; /* path: next-event estimation toward the environment image, MIS with the bsdf sample */
+       FRT_FLAG_ENV_SAMPLING = 2048,   /* path: next-event estimation toward the environment image, MIS with the bsdf sample */
+       FRT_FLAG_ROULETTE = 4096 };     /* path: Russian roulette from the fourth vertex on (below)        */
 
 /* FRT_FLAG_ENV_SAMPLING (frt_render, frt_render_device, frt_render_multi and
  * frt_selftest_path_host_env; fp32 and fp64).  Not the reference's estimator --
@@ -86,6 +87,30 @@ enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes
  *   no image (constant env_color), or an image without luminance: no effect,
  *     the film is that of the same call without the flag.
  *   ao, normals: no effect.
+ *   pssmlt: FRT_E_INVALID with a text in frt_last_error (its primary-sample
+ *     layout is the reference's). */
+
+/* FRT_FLAG_ROULETTE (frt_render, frt_render_device, frt_render_multi and
+ * frt_selftest_path_host[_env]; fp32 and fp64).  Not in the reference, whose
+ * path::Li follows every path until a light, the environment or max_depth ends
+ * it; the estimator has the same expectation and traces fewer rays per sample.
+ *   path: a scattering vertex at depth >= 3 (the camera ray's hit is depth 0;
+ *     the first three vertices never play -- the constant kRouletteDepth of
+ *     csrc/frt_path.hpp, not a parameter) lets the path go on with probability
+ *     q = min(1, largest component of the throughput the next ray would carry)
+ *     and divides that throughput by q; q == 1 changes nothing.  The decision
+ *     reads one random number of its own per vertex (RNG dimension 4 + 8 depth
+ *     + 2), so every other sample of the path is the one
+ *     the same call draws without the flag.  A path that stops still traces the
+ *     vertex's shadow ray and keeps its next-event term.  A zero bsdf pdf ends
+ *     the path as before.  The MIS weights, next-event estimation and max_depth
+ *     are unchanged; with max_depth <= 2 the film and the counters are those of
+ *     the call without the flag.
+ *     Works with constant environments, environment images and
+ *     FRT_FLAG_ENV_SAMPLING, on every plan, with sample_offset and shards.
+ *     The A/B register-cap flags (FRT_FLAG_WAVES4/5/6) do not apply: these
+ *     kernels have one cap per plan.
+ *   ao, normals: no effect, the film is that of the same call without the flag.
  *   pssmlt: FRT_E_INVALID with a text in frt_last_error (its primary-sample
  *     layout is the reference's). */
 

@@ -213,6 +213,10 @@ struct tile_gpu {
     // diffuse or rough vertex (FRT_FLAG_ENV_SAMPLING, frt.h) -- not the reference's estimator,
     // the same expectation with far less noise under a sun or a window; off by default
     bool env_sampling = false;
+    // path: Russian roulette from the fourth vertex on (FRT_FLAG_ROULETTE, frt.h) -- not in the
+    // reference; the same expectation with fewer rays per sample in closed scenes; off by
+    // default, on every device of `devices` when set; ao and normals ignore it
+    bool roulette = false;
     frt_stats last_stats{};
     static constexpr bool using_custom_viewer = false;
 
@@ -224,6 +228,7 @@ struct tile_gpu {
         p.max_depth = max_depth; p.integrator = INTEGRATOR; p.tile_size = tile_size;
         p.shard_index = 0; p.shard_count = 1;
         if (env_sampling) p.flags |= FRT_FLAG_ENV_SAMPLING;
+        if (roulette) p.flags |= FRT_FLAG_ROULETTE;
         std::vector<float> rgb((size_t)film->nx * film->ny * 3, 0.0f);
         check(frt_render_multi(gpus.data(), gpus.size(), &p, rgb.data(), &last_stats), "frt_render_multi",
               gpus.data()[0]);

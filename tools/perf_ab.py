@@ -52,6 +52,8 @@ def main():
              "no_oct": frt.FRT_FLAG_NO_OCT, "fp32": frt.FRT_FLAG_FP32}
     if hasattr(frt, "FRT_FLAG_ENV_SAMPLING"):   # (an older revision under FRT_PKG_ROOT has none: the variant is skipped)
         names["env_sampling"] = frt.FRT_FLAG_ENV_SAMPLING
+    if hasattr(frt, "FRT_FLAG_ROULETTE"):
+        names["roulette"] = frt.FRT_FLAG_ROULETTE
     flags = {}
     for v in args.variants.split(","):
         parts = v.split("/")[0].split("+")
