@@ -34,6 +34,7 @@ FRT_FLAG_FP64 = 512
 FRT_FLAG_FP32 = 1024
 FRT_FLAG_ENV_SAMPLING = 2048   # path: next-event estimation toward the environment image (frt.h)
 FRT_FLAG_ROULETTE = 4096       # path: Russian roulette from the fourth vertex on (frt.h)
+FRT_FLAG_SOBOL = 8192          # path: Owen-scrambled Sobol' sample points (frt.h)
 FRT_PRECISION_AUTO, FRT_PRECISION_FP32, FRT_PRECISION_FP64 = 0, 1, 2
 FRT_GPU_BVH_PLOC = 0
 FRT_GPU_BVH_LBVH = 1

@@ -145,6 +145,60 @@ FRT_HD float rng_u(RngKey k, uint32_t dim)
     return (float)(h >> 8) * (1.0f / 16777216.0f);
 }
 template <typename R> FRT_HD R rng_r(RngKey k, uint32_t dim) { return R(rng_u(k, dim)); }
+// ---------------------------------------------------------------------------
+// FRT_FLAG_SOBOL: the same (pixel, sample, dimension) stream drawn from padded
+// 2-D Owen-scrambled Sobol' points instead (Burley 2020, "Practical hash-based
+// Owen scrambling").  Dimensions 2j and 2j + 1 are the
+// two components of pair j's point with index `sample`: the first two Sobol'
+// dimensions, the index shuffled and each component scrambled per (frame
+// seed, pixel, pair), so any 2^m samples of a pixel starting at a multiple of
+// 2^m are a (0, m, 2)-net in every pair, and pairs, pixels and frames are
+// independent of one another.
+// ---------------------------------------------------------------------------
+FRT_HD uint32_t bitrev32(uint32_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __brev(x);                                   // v_bfrev_b32
+#else
+    x = (x >> 16) | (x << 16);
+    x = ((x & 0x00FF00FFU) << 8) | ((x >> 8) & 0x00FF00FFU);
+    x = ((x & 0x0F0F0F0FU) << 4) | ((x >> 4) & 0x0F0F0F0FU);
+    x = ((x & 0x33333333U) << 2) | ((x >> 2) & 0x33333333U);
+    return ((x & 0x55555555U) << 1) | ((x >> 1) & 0x55555555U);
+#endif
+}
+// the Laine-Karras permutation: bit b of the result depends on bits <= b of x
+// only, so on bit-reversed input it is a nested uniform (Owen) scramble
+FRT_HD uint32_t lk_perm(uint32_t x, uint32_t seed)
+{
+    x += seed;
+    x ^= x * 0x6c50b47cU; x ^= x * 0xb82f1e52U; x ^= x * 0xc7afe638U; x ^= x * 0x8d22f6e6U;
+    return x;
+}
+// k0 = the global sample index, k1 = the (frame seed, pixel) key
+FRT_HD RngKey sobol_key(uint32_t seed, uint32_t pixel, uint32_t sample)
+{
+    RngKey k;
+    k.k0 = sample;
+    k.k1 = mix32(mix32(seed ^ 0x2545F491U) + pixel * 0x9E3779B9U);
+    return k;
+}
+// the 32-bit word of dimension dim.  The pair's three seeds are derived here,
+// where they are used, so a path carries the two key words and nothing else.
+FRT_HD uint32_t sobol_word(RngKey k, uint32_t dim)
+{
+    const uint32_t h = mix32(k.k1 ^ ((dim >> 1) * 0x85EBCA77U + 0xC2B2AE3DU));   // the pair's shuffle seed
+    uint32_t r = lk_perm(bitrev32(k.k0), h);            // bitrev(idx), idx = owen(sample, h)
+    if (dim & 1u) {
+        // the second Sobol' dimension (columns v0 = 1 << 31, v(b+1) = v(b) ^ (v(b) >> 1))
+        // of idx, bit-reversed input: five butterfly stages; then owen(., seed_y)
+        r ^= (r << 1) & 0xAAAAAAAAU; r ^= (r << 2) & 0xCCCCCCCCU; r ^= (r << 4) & 0xF0F0F0F0U;
+        r ^= (r << 8) & 0xFF00FF00U; r ^= (r << 16) & 0xFFFF0000U;
+        return bitrev32(lk_perm(bitrev32(r), mix32(h ^ 0x7F4A7C15U)));
+    }
+    return bitrev32(lk_perm(bitrev32(r), mix32(h ^ 0x9E3779B9U)));   // van der Corput of idx, owen(., seed_x)
+}
+FRT_HD float sobol_u(RngKey k, uint32_t dim) { return (float)(sobol_word(k, dim) >> 8) * (1.0f / 16777216.0f); }
 // dimension layout: camera 0..3; bounce d: base 4 + 8d (+3 light pick,
 // +4..5 light sample, +6..7 bsdf direction; +0..2 reserved for get3d)
 FRT_HD uint32_t dim_bounce(int depth) { return 4u + 8u * (uint32_t)depth; }

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
     // The flushes round each contribution into the fp32 item sum, so a lean
     // plan's film equals the per-sample plans' to fp32 rounding, not bit for
     // bit (tests/test_gpu_parity.py::test_lean_plan_rounding).
-    constexpr bool kLean = !LDS_SCENE && (MATS & ~kMatsRoulette) == kMatsNone && KIND == FRT_INTEGRATOR_PATH && !kIsF64<R>;
+    constexpr bool kLean = !LDS_SCENE && (MATS & ~kMatsFeatures) == kMatsNone && KIND == FRT_INTEGRATOR_PATH && !kIsF64<R>;
     auto flush_L = [&]() {
         I.set(kIsAcc + 0, f2i(i2f(I.get(kIsAcc + 0)) + (float)P.L.x));
         I.set(kIsAcc + 1, f2i(i2f(I.get(kIsAcc + 1)) + (float)P.L.y));
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
             FRT_DIAG_TICK(4);
             pending = false;
             if constexpr (kLean)
-                P.key = rng_key(W.seed, (uint32_t)I.get(kIsPix), (uint32_t)(I.get(kIsCur) - 1) + W.s_off);
+                P.key = smp_key<MATS>(W.seed, (uint32_t)I.get(kIsPix), (uint32_t)(I.get(kIsCur) - 1) + W.s_off);
             const bool done = shade_kind<KIND, MATS>(P, S, T.h, W.max_depth, ne, ns);
             if (done || kLean) flush_L();   // fp32 chunk sums in either precision
             active = !done;
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
         const bool start = !active && have_item && I.get(kIsCur) < I.get(kIsEnd);
         if (start) {
             const int s_cur = I.get(kIsCur);
-            path_begin(P, S, I.get(kIsPx), I.get(kIsPy), W.nx, W.ny, W.seed, (uint32_t)I.get(kIsPix),
+            path_begin<MATS>(P, S, I.get(kIsPx), I.get(kIsPy), W.nx, W.ny, W.seed, (uint32_t)I.get(kIsPix),
                        (uint32_t)s_cur + W.s_off);
             I.set(kIsCur, s_cur + 1);
             active = true;

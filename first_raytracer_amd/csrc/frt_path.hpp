@@ -741,7 +741,26 @@ constexpr int kMatsEnvNee = 16;
 constexpr int kMatsRoulette = 32;
 // the first vertex (P.depth) that plays: the vertices at depth 0, 1, 2 never do
 constexpr int kRouletteDepth = 3;
+// kMatsSobol: the path integrator draws its sample points from Owen-scrambled
+// Sobol' pairs (FRT_FLAG_SOBOL; sobol_key / sobol_u, frt_device.hpp) instead of
+// the hash stream.  Only renders with that flag run these kernels; like
+// kMatsRoulette it adds no material.
+constexpr int kMatsSobol = 64;
+// the bits that change the estimator's bookkeeping, not the material set
+constexpr int kMatsFeatures = kMatsRoulette | kMatsSobol;
 constexpr int kMatsSpecAny = kMatsSpec | kMatsRough;
+// the sampler of a kernel set: the key of (frame seed, pixel, global sample
+// index) and the uniform of dimension dim (layout: dim_bounce)
+template <int MATS> FRT_HD RngKey smp_key(uint32_t seed, uint32_t pixel, uint32_t sample)
+{
+    if constexpr ((MATS & kMatsSobol) != 0) return sobol_key(seed, pixel, sample);
+    else return rng_key(seed, pixel, sample);
+}
+template <int MATS, typename R> FRT_HD R smp_r(RngKey k, uint32_t dim)
+{
+    if constexpr ((MATS & kMatsSobol) != 0) return R(sobol_u(k, dim));
+    else return rng_r<R>(k, dim);
+}
 
 // ---- textures (texture.h:30-49), MATS kernels only ----
 // (int)x as the reference's x86-64 build computes it (cvttsd2si): NaN and
@@ -942,17 +961,17 @@ template <typename R> struct PathState {
 };
 
 // path.cpp:129-136 + camera.h:30-35 (+ util.h:21-41 thin lens)
-template <typename R>
+template <int MATS = kMatsNone, typename R>
 FRT_HD void path_begin(PathState<R> &P, const DevScene &S, int px, int py, int nx, int ny, uint32_t seed,
                        uint32_t pixel, uint32_t sample)
 {
-    P.key = rng_key(seed, pixel, sample);
+    P.key = smp_key<MATS>(seed, pixel, sample);
     const CamView<R> cam = cam_view<R>(S);
-    const R u = fdiv((R)px + rng_r<R>(P.key, 0), (R)nx);
-    const R v = fdiv((R)py + rng_r<R>(P.key, 1), (R)ny);
+    const R u = fdiv((R)px + smp_r<MATS, R>(P.key, 0), (R)nx);
+    const R v = fdiv((R)py + smp_r<MATS, R>(P.key, 1), (R)ny);
     V3<R> off = zero3<R>();
     if (cam.lens_r != R(0)) {
-        const R a = rng_r<R>(P.key, 2) * R(2) - R(1), b = rng_r<R>(P.key, 3) * R(2) - R(1);
+        const R a = smp_r<MATS, R>(P.key, 2) * R(2) - R(1), b = smp_r<MATS, R>(P.key, 3) * R(2) - R(1);
         R rx = R(0), ry = R(0);
         if (a != R(0) || b != R(0)) {
             R r, phi;
@@ -1125,14 +1144,14 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     SpecMat M{};
     if (!(MATS & kMatsSpecAny) || lamb) {               // cosine_pdf (path.cpp:96-110)
         const Onb<R> uvw = onb_from_w(n);
-        wo = onb_local(uvw, cosine_direction(rng_r<R>(P.key, base + 6), rng_r<R>(P.key, base + 7)));
+        wo = onb_local(uvw, cosine_direction(smp_r<MATS, R>(P.key, base + 6), smp_r<MATS, R>(P.key, base + 7)));
         const R cw = dot(n, normalize(wo));
         pdf = vmax(cw, R(0)) * Cst<R>::inv_pi;
         beta_next = fdiv(vabs(cw), pdf) * (P.beta * (Cst<R>::inv_pi * rgb<R>(m0)));   // lambertian::eval_bsdf
     } else {                                            // specular branch (path.cpp:78-95); the
         M = spec_mat(S, mat, mtype, m0, m1);            // scatter sample is get3d's (base + 0, 1)
         R sampled;
-        wo = spec_generate<MATS>(M, n, wi, rng_r<R>(P.key, base + 0), rng_r<R>(P.key, base + 1), sampled);
+        wo = spec_generate<MATS>(M, n, wi, smp_r<MATS, R>(P.key, base + 0), smp_r<MATS, R>(P.key, base + 1), sampled);
         pdf = spec_value<MATS>(M, n, wi, wo);
         if (sampled > R(0)) pdf = sampled;              // path.cpp:82
         const V3<R> bsdf = spec_eval<MATS>(M, n, wi, wo);
@@ -1143,7 +1162,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     // dot(n, wo); the constant lets the compiler drop the state.
     // NEE's light pick (path.cpp:39-40)
     const int nl = S.n_lights;
-    R pick = rng_r<R>(P.key, base + 3);
+    R pick = smp_r<MATS, R>(P.key, base + 3);
     // kEnvNee: a lambertian or rough conductor vertex -- the ones whose next hit is
     // MIS-weighted -- samples the image instead, always in a scene without lights,
     // else with probability 1/2; the rescaled remainder then feeds the reference's
@@ -1173,7 +1192,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
     if constexpr (kRoulette) {
         if (!zero_pdf && P.depth >= kRouletteDepth) {
             const R q = vmin(R(1), vmax(beta_next.x, vmax(beta_next.y, beta_next.z)));
-            if (!(rng_r<R>(P.key, base + 2) < q)) P.term = true;
+            if (!(smp_r<MATS, R>(P.key, base + 2) < q)) P.term = true;
             else beta_next = rcp(q) * beta_next;
         }
     }
@@ -1188,7 +1207,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
         // toward the drawn texel: its radiance and density, the bsdf terms of the
         // area-light branch below; a lambertian vertex takes no light from under
         // its shading normal (its bsdf sample never goes there)
-        const EnvSample<R> e = env_sample(S, rng_r<R>(P.key, base + 4), rng_r<R>(P.key, base + 5));
+        const EnvSample<R> e = env_sample(S, smp_r<MATS, R>(P.key, base + 4), smp_r<MATS, R>(P.key, base + 5));
         const R cos_wi = dot(n, e.d);
         const bool l = !(MATS & kMatsSpecAny) || lamb;
         P.nee = zero3<R>();
@@ -1204,7 +1223,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
         const int lref = S.lights[idx];
         V3<R> ln;
         int lmat;
-        const V3<R> tl = prim_sample(S, lref, nee_o, rng_r<R>(P.key, base + 4), rng_r<R>(P.key, base + 5), ln, lmat);
+        const V3<R> tl = prim_sample(S, lref, nee_o, smp_r<MATS, R>(P.key, base + 4), smp_r<MATS, R>(P.key, base + 5), ln, lmat);
         const R dist2 = len2(tl);
         const V3<R> tu = rlen(tl) * tl;
         const R cos_wi = dot(n, tu);
@@ -1267,7 +1286,7 @@ FRT_HD bool ao_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, uint32
     const float4 m0 = S.mats[kMatStride * mat], m1 = S.mats[kMatStride * mat + 1];
     const int mtype = f2i(m0.w);
     const uint32_t base = dim_bounce(0);
-    const R u0 = rng_r<R>(P.key, base + 6), u1 = rng_r<R>(P.key, base + 7);
+    const R u0 = smp_r<MATS, R>(P.key, base + 6), u1 = smp_r<MATS, R>(P.key, base + 7);
     V3<R> wo;
     if (mtype == FRT_MAT_LAMBERTIAN) {
         wo = onb_local(onb_from_w(n), cosine_direction(u0, u1));

@@ -92,6 +92,7 @@ constexpr bool kSplitLds = true;
 namespace frt_lds {
 int path_oct(int stack, int waves, size_t scene_bytes, Launcher &L);
 int path_oct_roulette(int stack, size_t scene_bytes, Launcher &L);   // FRT_FLAG_ROULETTE: the 5-wave kernels
+int path_oct_sobol(int stack, bool roulette, size_t scene_bytes, Launcher &L);   // FRT_FLAG_SOBOL [| _ROULETTE]: the same
 int mlt_oct(int stack, const void **boot, const void **chains);
 }  // namespace frt_lds
 
@@ -213,10 +214,13 @@ static int pick_launcher_f64_t(const frt_ctx *c, Launcher &L)
 // context can have is covered: the flag never falls back to a kernel without
 // roulette.  The octant plan's lambertian kernels come from frt_lds
 // (path_oct_roulette), under that unit's scheduler flag.
+// The kMatsSobol kernels (FRT_FLAG_SOBOL, with or without roulette) take the
+// same plans with the same caps: MATS then carries kMatsSobol, and the octant
+// plan's lambertian kernels are frt_lds::path_oct_sobol's.
 template <int MATS, int W_LDS, int W_HBM, int W_WIDE>
 static int pick_launcher_roulette_t(const frt_ctx *c, int flags, Launcher &L)
 {
-    static_assert((MATS & kMatsRoulette) != 0, "the roulette kernels' plans");
+    static_assert((MATS & kMatsFeatures) != 0, "the roulette and Sobol' kernels' plans");
     if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, MATS>(0); return FRT_OK; }
     const int d = c->stack_needed;
     const size_t sb = c->scene_lds_bytes;
@@ -224,6 +228,8 @@ static int pick_launcher_roulette_t(const frt_ctx *c, int flags, Launcher &L)
     if (oct) {
         if constexpr (MATS == kMatsRoulette && kSplitLds) {
             return frt_lds::path_oct_roulette(d < 8 ? 8 : 16, c->scene_lds_bytes_oct, L);
+        } else if constexpr ((MATS & ~kMatsRoulette) == kMatsSobol && kSplitLds) {
+            return frt_lds::path_oct_sobol(d < 8 ? 8 : 16, (MATS & kMatsRoulette) != 0, c->scene_lds_bytes_oct, L);
         } else {
             L = d < 8 ? make_launcher<8, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct)
                       : make_launcher<16, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct);
@@ -249,7 +255,7 @@ static int pick_launcher_roulette_t(const frt_ctx *c, int flags, Launcher &L)
 template <int MATS>
 static int pick_launcher_roulette_f64_t(const frt_ctx *c, Launcher &L)
 {
-    static_assert((MATS & kMatsRoulette) != 0, "the roulette kernels' plans");
+    static_assert((MATS & kMatsFeatures) != 0, "the roulette and Sobol' kernels' plans");
     if (c->world_kind == FRT_WORLD_LIST)
         L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, MATS, FRT_INTEGRATOR_PATH, double>(0);
     else if (c->stack_needed < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
@@ -276,6 +282,9 @@ int pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher &L);
 // the lambertian ones without an image (those: the main unit and frt_lds);
 // env_sampling: the kernels that also sample the image
 int pick_roulette(const frt_ctx *c, int flags, bool f64, bool env_sampling, Launcher &L);
+// the path kernels of FRT_FLAG_SOBOL (roulette: with FRT_FLAG_ROULETTE as well) of the
+// same scenes, on the same plans and caps
+int pick_sobol(const frt_ctx *c, int flags, bool f64, bool env_sampling, bool roulette, Launcher &L);
 // PSS-MLT with the material branch or (env) the environment image, for the
 // (stack, world, lds) plans of render_mlt
 int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);

@@ -367,6 +367,18 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
 static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64, bool env_sampling)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
+    if ((flags & FRT_FLAG_SOBOL) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsSobol kernels, the roulette kernels' plans
+        const bool rl = (flags & FRT_FLAG_ROULETTE) != 0;
+        if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
+            return frt_mats::pick_sobol(c, flags, f64, env_sampling, rl, L);
+        if (f64) {   // a lambertian list world
+            if (rl) L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsSobol | kMatsRoulette, FRT_INTEGRATOR_PATH, double>(0);
+            else L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsSobol, FRT_INTEGRATOR_PATH, double>(0);
+            return FRT_OK;
+        }
+        return rl ? pick_launcher_roulette_t<kMatsSobol | kMatsRoulette, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L)
+                  : pick_launcher_roulette_t<kMatsSobol, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L);
+    }
     if ((flags & FRT_FLAG_ROULETTE) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsRoulette kernels
         if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
             return frt_mats::pick_roulette(c, flags, f64, env_sampling, L);
@@ -757,6 +769,9 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     HIPCHK(c, hipSetDevice(c->device));
     c->mlt_rows = 0;                                   // `partial` is about to be reused
     if (p->integrator == FRT_INTEGRATOR_PSSMLT) {
+        if (p->flags & FRT_FLAG_SOBOL)
+            return set_err(c, FRT_E_INVALID, "FRT_FLAG_SOBOL: pssmlt draws its primary samples from the hash stream "
+                                             "(its sample layout and mutations are the reference's); render without the flag");
         if (p->flags & FRT_FLAG_ROULETTE)
             return set_err(c, FRT_E_INVALID, "FRT_FLAG_ROULETTE: pssmlt plays no Russian roulette "
                                              "(its primary-sample layout is the reference's); render without the flag");

@@ -34,3 +34,20 @@ int frt_lds::path_oct_roulette(int stack, size_t scene_bytes, Launcher &L)
     return FRT_OK;
 #endif
 }
+// ... and with the Sobol' sampler (FRT_FLAG_SOBOL), with or without roulette: the same cap
+template <int MATS> static int path_oct_sobol_t(int stack, size_t scene_bytes, Launcher &L)
+{
+    if (stack == 8) L = make_launcher<8, kWorldBvh2Oct, true, 5, MATS>(scene_bytes);
+    else if (stack == 16) L = make_launcher<16, kWorldBvh2Oct, true, 5, MATS>(scene_bytes);
+    else return FRT_E_UNSUPPORTED;
+    return FRT_OK;
+}
+int frt_lds::path_oct_sobol(int stack, bool roulette, size_t scene_bytes, Launcher &L)
+{
+#if defined(FRT_OCT_IN_MAIN)
+    return FRT_E_UNSUPPORTED;
+#else
+    return roulette ? path_oct_sobol_t<kMatsSobol | kMatsRoulette>(stack, scene_bytes, L)
+                    : path_oct_sobol_t<kMatsSobol>(stack, scene_bytes, L);
+#endif
+}

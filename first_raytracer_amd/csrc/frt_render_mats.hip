@@ -96,6 +96,20 @@ int frt_mats::pick_roulette(const frt_ctx *c, int flags, bool f64, bool env_samp
     if (c->env_texels) return pick_roulette_t<kMatsAll | kMatsEnv | kMatsRoulette>(c, flags, f64, L);
     return pick_roulette_t<kMatsAll | kMatsRoulette>(c, flags, f64, L);
 }
+// ... and with FRT_FLAG_SOBOL (the kMatsSobol kernels), alone or with roulette: the same
+// material sets, plans and caps
+template <int EXTRA>
+static int pick_sobol_t(const frt_ctx *c, int flags, bool f64, bool env_sampling, Launcher &L)
+{
+    if (env_sampling) return pick_roulette_t<kMatsNee | EXTRA>(c, flags, f64, L);
+    if (c->env_texels) return pick_roulette_t<kMatsAll | kMatsEnv | EXTRA>(c, flags, f64, L);
+    return pick_roulette_t<kMatsAll | EXTRA>(c, flags, f64, L);
+}
+int frt_mats::pick_sobol(const frt_ctx *c, int flags, bool f64, bool env_sampling, bool roulette, Launcher &L)
+{
+    return roulette ? pick_sobol_t<kMatsSobol | kMatsRoulette>(c, flags, f64, env_sampling, L)
+                    : pick_sobol_t<kMatsSobol>(c, flags, f64, env_sampling, L);
+}
 template <bool MATS, bool ENV>
 static int mlt_pick(int stack, int world, bool lds, const void **boot, const void **chains)
 {

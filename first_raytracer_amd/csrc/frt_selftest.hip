@@ -26,7 +26,7 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
         V3<R> acc = zero3<R>();
         for (int smp = 0; smp < p->spp; ++smp) {
             PathState<R> P;
-            path_begin(P, S, px, py, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)(smp + p->sample_offset));
+            path_begin<MATS>(P, S, px, py, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)(smp + p->sample_offset));
             ++cnt[0];
             for (;;) {
                 Hit<R> h;
@@ -99,21 +99,24 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
     uint64_t cnt[3] = {0, 0, 0};   // camera, extension, shadow
     constexpr int kEnvAll = kMatsAll | kMatsEnv;   // with an image: the code of the kMatsEnv kernels
     constexpr int kEnvNee = kEnvAll | kMatsEnvNee;   // ... and of the kernels that sample it
-    // FRT_FLAG_ROULETTE (path): the code of the kMatsRoulette kernels
-    constexpr int kRl = kMatsRoulette;
-    const bool roulette = (p->flags & FRT_FLAG_ROULETTE) && p->integrator == FRT_INTEGRATOR_PATH;
-    if (roulette && f64 && env_sampling) selftest_pixels<double, kEnvNee | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (roulette && env_sampling) selftest_pixels<float, kEnvNee | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (roulette && f64 && env) selftest_pixels<double, kEnvAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (roulette && f64) selftest_pixels<double, kMatsAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (roulette && env) selftest_pixels<float, kEnvAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (roulette) selftest_pixels<float, kMatsAll | kRl>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (f64 && env_sampling) selftest_pixels<double, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (env_sampling) selftest_pixels<float, kEnvNee>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (f64 && env) selftest_pixels<double, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (f64) selftest_pixels<double>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else if (env) selftest_pixels<float, kEnvAll>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-    else selftest_pixels<float>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+    // FRT_FLAG_ROULETTE, FRT_FLAG_SOBOL (path): the code of the kMatsRoulette / kMatsSobol kernels
+    const bool path = p->integrator == FRT_INTEGRATOR_PATH;
+    const bool roulette = (p->flags & FRT_FLAG_ROULETTE) && path, sobol = (p->flags & FRT_FLAG_SOBOL) && path;
+    auto run_set = [&](auto extra) {                    // the material set, then the precision
+        constexpr int X = decltype(extra)::value;
+        auto run = [&](auto mats) {
+            constexpr int M = decltype(mats)::value;
+            if (f64) selftest_pixels<double, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+            else selftest_pixels<float, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+        };
+        if (env_sampling) run(std::integral_constant<int, kEnvNee>{});
+        else if (env) run(std::integral_constant<int, kEnvAll>{});
+        else run(std::integral_constant<int, kMatsAll>{});
+    };
+    if (sobol && roulette) run_set(std::integral_constant<int, kMatsSobol | kMatsRoulette>{});
+    else if (sobol) run_set(std::integral_constant<int, kMatsSobol>{});
+    else if (roulette) run_set(std::integral_constant<int, kMatsRoulette>{});
+    else run_set(std::integral_constant<int, 0>{});
     if (st) {
         memset(st, 0, sizeof(*st));
         st->camera_rays = cnt[0]; st->extension_rays = cnt[1]; st->shadow_rays = cnt[2];

@@ -4,7 +4,7 @@
 //
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
 //              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals] [--chains 262144]
-//              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--out out.pfm] [--png out.png] [--bvh reference|sah]
+//              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
@@ -17,6 +17,8 @@
 //   sampling, pssmlt keeps the reference's sample layout).
 // --roulette: path plays Russian roulette from the fourth vertex on (FRT_FLAG_ROULETTE:
 //   the same expectation, fewer rays per sample in closed scenes); the path integrator only.
+// --sobol: path draws its sample points from Owen-scrambled Sobol' pairs (FRT_FLAG_SOBOL: the
+//   same expectation, less noise per sample); the path integrator only.
 // --png: also the tonemapped display image (viewer::add_sample bytes, image::save_image).
 // --bvh sah: rebuild the scene's BVH with the binned SAH builder (faster traversal;
 //   exact-t ties then follow that tree's order instead of create_bvh's).
@@ -34,7 +36,7 @@ int main(int argc, char **argv)
     long ns = 100;
     unsigned seed = 0;
     double env[3] = {0, 0, 0};
-    bool has_env = false, env_sampling = false, roulette = false;
+    bool has_env = false, env_sampling = false, roulette = false, sobol = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -59,6 +61,7 @@ int main(int argc, char **argv)
         else if (a == "--env-map") env_map = next();
         else if (a == "--env-sampling") env_sampling = true;
         else if (a == "--roulette") roulette = true;
+        else if (a == "--sobol") sobol = true;
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -70,6 +73,10 @@ int main(int argc, char **argv)
     }
     if (roulette && integrator != "path") {
         std::fprintf(stderr, "--roulette: only --integrator path plays Russian roulette\n");
+        return 2;
+    }
+    if (sobol && integrator != "path") {
+        std::fprintf(stderr, "--sobol: only --integrator path draws Sobol' sample points\n");
         return 2;
     }
     try {
@@ -97,6 +104,7 @@ int main(int argc, char **argv)
             frt::renderer<frt::path_gpu> render;
             render.env_sampling = env_sampling;
             render.roulette = roulette;
+            render.sobol = sobol;
             run(render);
         } else if (integrator == "ao") {
             frt::renderer<frt::ao_gpu> render;

@@ -62,7 +62,8 @@ enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes
        FRT_FLAG_FP64 = 512,            /* path: the fp64 kernel for this call (self-test: fp64 host replay) */
        FRT_FLAG_FP32 = 1024,           /* path: the fp32 kernels even where the precision picks fp64      */
        FRT_FLAG_ENV_SAMPLING = 2048,   /* path: next-event estimation toward the environment image, MIS with the bsdf sample */
-       FRT_FLAG_ROULETTE = 4096 };     /* path: Russian roulette from the fourth vertex on (below)        */
+       FRT_FLAG_ROULETTE = 4096,       /* path: Russian roulette from the fourth vertex on (below)        */
+       FRT_FLAG_SOBOL = 8192 };        /* path: Owen-scrambled Sobol' sample points (below)               */
 
 /* FRT_FLAG_ENV_SAMPLING (frt_render, frt_render_device, frt_render_multi and
  * frt_selftest_path_host_env; fp32 and fp64).  Not the reference's estimator --
@@ -113,6 +114,31 @@ enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes
  *   ao, normals: no effect, the film is that of the same call without the flag.
  *   pssmlt: FRT_E_INVALID with a text in frt_last_error (its primary-sample
  *     layout is the reference's). */
+
+/* FRT_FLAG_SOBOL (frt_render, frt_render_device, frt_render_multi and
+ * frt_selftest_path_host[_env]; fp32 and fp64).  Not in the reference, whose
+ * samplers draw every dimension independently; the estimator and its
+ * expectation are unchanged, only the sample points are.
+ *   path: dimension d of the sample with global index s (sample_offset + the
+ *     local index) of a pixel is component d & 1 of a 2-D Owen-scrambled Sobol'
+ *     point: the point with index s of pair d >> 1, pairs padded in the manner
+ *     of Burley 2020 -- each pair the first two Sobol' dimensions with its own
+ *     shuffle of the index and its own two scrambles, hashed from (seed, pixel,
+ *     pair); the exact construction is DESIGN.md section 4.  The dimension
+ *     layout is the one without the flag, so film position, lens, light point,
+ *     image texel and bsdf direction are each one stratified pair, and roulette
+ *     and light pick share one.  Any 2^m consecutive samples of a pixel that
+ *     start at a multiple of 2^m are a (0, m, 2)-net in every pair: progressive
+ *     passes (sample_offset) of power-of-two length keep the property, and k
+ *     passes of n samples are the one call of k n samples.  Different seeds give
+ *     independent scrambles, so averages over seeds keep their standard error.
+ *     Works with FRT_FLAG_ROULETTE, constant environments, environment images
+ *     and FRT_FLAG_ENV_SAMPLING, on every plan, with sample_offset and shards.
+ *     The A/B register-cap flags (FRT_FLAG_WAVES4/5/6) do not apply: these
+ *     kernels have one cap per plan.
+ *   ao, normals: no effect, the film is that of the same call without the flag.
+ *   pssmlt: FRT_E_INVALID with a text in frt_last_error (its primary samples
+ *     are the hash stream's, mutated as the reference does). */
 
 /* Kernel precision (frt_set_precision).  The reference computes in fp64
  * (geometry.h:351).  FRT_PRECISION_AUTO: fp64 for list worlds (hitable_list,

@@ -217,6 +217,10 @@ struct tile_gpu {
     // reference; the same expectation with fewer rays per sample in closed scenes; off by
     // default, on every device of `devices` when set; ao and normals ignore it
     bool roulette = false;
+    // path: Owen-scrambled Sobol' sample points instead of independent hashes (FRT_FLAG_SOBOL,
+    // frt.h) -- not in the reference; the same expectation with less noise per sample; off by
+    // default, on every device of `devices` when set; ao and normals ignore it
+    bool sobol = false;
     frt_stats last_stats{};
     static constexpr bool using_custom_viewer = false;
 
@@ -229,6 +233,7 @@ struct tile_gpu {
         p.shard_index = 0; p.shard_count = 1;
         if (env_sampling) p.flags |= FRT_FLAG_ENV_SAMPLING;
         if (roulette) p.flags |= FRT_FLAG_ROULETTE;
+        if (sobol) p.flags |= FRT_FLAG_SOBOL;
         std::vector<float> rgb((size_t)film->nx * film->ny * 3, 0.0f);
         check(frt_render_multi(gpus.data(), gpus.size(), &p, rgb.data(), &last_stats), "frt_render_multi",
               gpus.data()[0]);

@@ -54,6 +54,8 @@ def main():
         names["env_sampling"] = frt.FRT_FLAG_ENV_SAMPLING
     if hasattr(frt, "FRT_FLAG_ROULETTE"):
         names["roulette"] = frt.FRT_FLAG_ROULETTE
+    if hasattr(frt, "FRT_FLAG_SOBOL"):
+        names["sobol"] = frt.FRT_FLAG_SOBOL
     flags = {}
     for v in args.variants.split(","):
         parts = v.split("/")[0].split("+")
