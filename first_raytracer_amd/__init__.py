@@ -40,6 +40,8 @@ FRT_GPU_BVH_PLOC = 0
 FRT_GPU_BVH_LBVH = 1
 FRT_GPU_BVH_SAH = 2
 FRT_INTEGRATOR_PATH, FRT_INTEGRATOR_PSSMLT, FRT_INTEGRATOR_AO, FRT_INTEGRATOR_NORMALS = 0, 1, 2, 3
+# first-hit feature images and the feature-guided film filter (frt.h; not in the reference)
+FRT_INTEGRATOR_ALBEDO, FRT_INTEGRATOR_DEPTH, FRT_INTEGRATOR_DENOISE = 4, 5, 6
 
 ERRORS = {0: "ok", -1: "invalid", -2: "hip", -3: "no scene", -4: "unsupported", -5: "io", -6: "no gfx950 device"}
 
@@ -136,7 +138,8 @@ class RenderParams(ctypes.Structure):
     @classmethod
     def make(cls, nx, ny, spp, seed=0, max_depth=33, tile_size=32, shard_index=0, shard_count=1,
              samples_per_item=0, flags=0, integrator=0, sample_offset=0):
-        """integrator: FRT_INTEGRATOR_PATH (path.cpp), _AO (ao.cpp) or _NORMALS (debug_renderer.h);
+        """integrator: FRT_INTEGRATOR_PATH (path.cpp), _AO (ao.cpp), _NORMALS (debug_renderer.h),
+        _ALBEDO / _DEPTH (first-hit feature images) or _DENOISE (Context.denoise);
         sample_offset: first global sample index (progressive passes)."""
         return cls(nx=nx, ny=ny, spp=spp, seed=seed, max_depth=max_depth, integrator=integrator, tile_size=tile_size,
                    shard_index=shard_index, shard_count=shard_count, samples_per_item=samples_per_item, flags=flags,
@@ -461,6 +464,15 @@ class Context:
         _check(lib().frt_render(self.ptr, ctypes.byref(params), film.ctypes.data, ctypes.byref(st)),
                "frt_render", self.ptr)
         return film, st
+
+    def denoise(self, film, nx, ny, spp=16, seed=0, tile_size=32, flags=0):
+        """FRT_INTEGRATOR_DENOISE: filter the finished colour film (ny, nx, 3) float32 -- finite
+        and >= 0 (a path film can hold values a few 1e-6 below 0: np.maximum(film, 0) first), from
+        path, accumulated passes or pssmlt -- in place, guided by spp-sample normals, albedo and
+        depth renders of the uploaded scene.  Returns (film, stats)."""
+        p = RenderParams.make(nx, ny, spp, seed=seed, tile_size=tile_size, flags=flags,
+                              integrator=FRT_INTEGRATOR_DENOISE)
+        return self.render(p, film=film)
 
     def render_device(self, params, dev_ptr, stream_ptr=None):
         """Render this shard's slots into device memory at dev_ptr (slot_count*3 floats)."""

@@ -50,6 +50,10 @@ struct frt_ctx {
     unsigned long long *wave_rays = nullptr; size_t wave_rays_n = 0;
     float *slots_out = nullptr; size_t slots_out_bytes = 0;
     unsigned long long *splat = nullptr; size_t splat_bytes = 0;   // PSS-MLT fixed-point splat film
+    // FRT_INTEGRATOR_DENOISE: the three feature films in slot order, and the pixel-order planes
+    // of the filter (the packed guides and the two iterates, frt_denoise.hip)
+    float *dn_feat = nullptr; size_t dn_feat_bytes = 0;
+    float4 *dn_planes = nullptr; size_t dn_planes_bytes = 0;
     // frt_render_multi on this context as shard 0: RCCL communicators over the
     // member devices (one per member, cached while the device list is the
     // same), the gather buffer and the device film
@@ -105,4 +109,11 @@ bool params_ok(const frt_render_params *p);
 int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats);
 // frt_multi.hip
 void free_comms(frt_ctx *c);
+// frt_denoise.hip: the filter of FRT_INTEGRATOR_DENOISE over a whole frame in slot order (shard 0
+// of 1) -- colour_slots in place, guided by the three feature films in the same order; *ms gets
+// the device time of its kernels
+namespace frt_denoise {
+int run(frt_ctx *c, const frt_render_params *p, float *colour_slots, const float *normals_slots,
+        const float *albedo_slots, const float *depth_slots, uint32_t n_slots, hipStream_t st, float *ms);
+}
 #pragma GCC visibility pop

@@ -91,6 +91,8 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
     frt_ctx *c0 = ctxs[0];
     if (!params_ok(p) || p->shard_count != 1 || p->shard_index != 0)
         return set_err(c0, FRT_E_INVALID, "frt_render_multi: params must describe the whole frame (shard 0 of 1)");
+    // the filter's stencil crosses tiles, and its feature passes are a small part of a frame: one context
+    if (p->integrator == FRT_INTEGRATOR_DENOISE) return frt_render(c0, p, film_rgb, st);
     for (int i = 1; i < n; ++i)   // the environment image is context state: every member needs the same one
         if (ctxs[i]->env_nx != c0->env_nx || ctxs[i]->env_ny != c0->env_ny || ctxs[i]->env_hash != c0->env_hash)
             return set_err(c0, FRT_E_INVALID, "frt_render_multi: the contexts hold different environment images "

@@ -1337,12 +1337,69 @@ template <int MATS = kMatsAll, typename R> FRT_HD bool normals_shade(PathState<R
     return true;
 }
 
+// ---- first-hit feature images (not in the reference; frt.h) ----
+
+// FRT_INTEGRATOR_ALBEDO: the reflectance colour at the camera hit -- the
+// material's colour with its texture as path_shade sees it; 1 on a light and on
+// a miss (radiance is not reflectance).  The texture code is always compiled
+// in (apply_texture returns at once for a constant one), so one kernel set
+// serves every scene, and the environment is never read.
+template <typename R> FRT_HD bool albedo_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h)
+{
+    P.L = V3<R>{R(1), R(1), R(1)};
+    if (h.prim < 0) return true;
+    const V3<R> p = P.ro + h.t * P.rd;
+    V3<R> n;
+    int mat;
+    prim_shade(S, h.prim, P.ro, p, h.u, h.v, n, mat);
+    float4 m0 = S.mats[kMatStride * mat], m1 = S.mats[kMatStride * mat + 1];
+    const int mtype = f2i(m0.w);
+    if (mtype == FRT_MAT_DIFFUSE_LIGHT) return true;
+    apply_texture(S, mat, mtype, h.prim, p, h.u, h.v, m0, m1);
+    if (mtype == FRT_MAT_LAMBERTIAN || mtype == FRT_MAT_METAL) {
+        P.L = rgb<R>(m0);
+    } else if (mtype == FRT_MAT_MODIFIED_PHONG) {
+        const V3<R> a = rgb<R>(m0) + rgb<R>(m1);
+        P.L = V3<R>{vmin(R(1), a.x), vmin(R(1), a.y), vmin(R(1), a.z)};
+    } else {                                            // dielectric, rough_conductor: specular reflectance
+        P.L = rgb<R>(m1);
+    }
+    return true;
+}
+
+// FRT_INTEGRATOR_DEPTH: (t, t^2, 1) at a hit, t the distance from the lens point
+// along the (unnormalised) camera ray; 0 on a miss.  The film's z is coverage.
+template <typename R> FRT_HD bool depth_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h)
+{
+    P.L = zero3<R>();
+    if (h.prim < 0) return true;
+    const R t = h.t * fsqrt(len2(P.rd));
+    P.L = V3<R>{t, t * t, R(1)};
+    return true;
+}
+
+// The depth film's (x, y, k) = (mean t hit, mean t^2 hit, mean hit) obey y k >= x^2, and the
+// fp32 sums can miss that by an ulp of y.  The film's y is raised to the next float that keeps
+// it on the stored values (in fp64), so a variance y / k - (x / k)^2 taken from the film is
+// never negative.
+FRT_HD float depth_moment_floor(float x, float y, float k)
+{
+    if (!(k > 0.0f)) return y;
+    const double lo = (double)x * (double)x / (double)k;
+    if ((double)y >= lo) return y;
+    float r = (float)lo;
+    if ((double)r < lo) r += r * 1.1920929e-7f;         // one or two ulps up
+    return r;
+}
+
 // integrator dispatch of the megakernel / self-test (KIND = FRT_INTEGRATOR_*)
 template <int KIND, int MATS, typename R>
 FRT_HD bool shade_kind(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
     if constexpr (KIND == FRT_INTEGRATOR_AO) return ao_shade<MATS>(P, S, h, n_sh);
     else if constexpr (KIND == FRT_INTEGRATOR_NORMALS) return normals_shade<MATS>(P, S, h);
+    else if constexpr (KIND == FRT_INTEGRATOR_ALBEDO) return albedo_shade(P, S, h);
+    else if constexpr (KIND == FRT_INTEGRATOR_DEPTH) return depth_shade(P, S, h);
     else return path_shade<MATS>(P, S, h, max_depth, n_ext, n_sh);
 }
 

@@ -289,3 +289,12 @@ int pick_sobol(const frt_ctx *c, int flags, bool f64, bool env_sampling, bool ro
 // (stack, world, lds) plans of render_mlt
 int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);
 }  // namespace frt_mats
+
+// the feature unit's entry point (frt_render_feat.hip): the kernels of
+// FRT_INTEGRATOR_ALBEDO and FRT_INTEGRATOR_DEPTH, on the plans of normals
+// (pick_launcher_kind).  One kernel set for every scene and context: albedo
+// always carries the texture lookup, and neither reads the environment, so a
+// context with an image runs them too (no kMatsEnv variant).
+namespace frt_feat {
+int pick(const frt_ctx *c, int integrator, int flags, Launcher &L);
+}  // namespace frt_feat

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -39,6 +40,37 @@ __global__ void film_reduce(const float *__restrict__ partial, float *__restrict
         }
         const float k = 1.0f / (float)spp;
         r *= k; g *= k; b *= k;
+    }
+    out[3ull * s + 0] = r;
+    out[3ull * s + 1] = g;
+    out[3ull * s + 2] = b;
+}
+
+// ... of the feature integrators (albedo, depth): sum / spp, so that a pixel whose every
+// sample added exactly 1 (depth's coverage, a white albedo) is exactly 1.0f at any spp,
+// which spp * (1 / spp) is not.  moments: the depth film, whose second moment keeps
+// y k >= x^2 (depth_moment_floor).
+__global__ void film_reduce_mean(const float *__restrict__ partial, float *__restrict__ out, uint32_t n_slots,
+                                 int n_chunks, int spp, int tile, int ntx, int shard_index, int shard_count, int nx, int ny,
+                                 int moments)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    const int T2 = tile * tile;
+    const int t_ord = (int)(s / (uint32_t)T2), sl = (int)(s % (uint32_t)T2);
+    const int tile_id = shard_index + t_ord * shard_count;
+    int lx, ly;
+    slot_to_local(sl, tile, lx, ly);
+    const int px = (tile_id % ntx) * tile + lx, py = (tile_id / ntx) * tile + ly;
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (px < nx && py < ny) {
+        for (int c = 0; c < n_chunks; ++c) {
+            const float *q = partial + 3ull * ((size_t)c * n_slots + s);
+            r += q[0]; g += q[1]; b += q[2];
+        }
+        const float n = (float)spp;
+        r /= n; g /= n; b /= n;
+        if (moments) g = depth_moment_floor(r, g, b);
     }
     out[3ull * s + 0] = r;
     out[3ull * s + 1] = g;
@@ -108,6 +140,8 @@ extern "C" int frt_destroy(frt_ctx *c)
     if (c->wave_rays) (void)hipFree(c->wave_rays);
     if (c->slots_out) (void)hipFree(c->slots_out);
     if (c->splat) (void)hipFree(c->splat);
+    if (c->dn_feat) (void)hipFree(c->dn_feat);
+    if (c->dn_planes) (void)hipFree(c->dn_planes);
     if (c->env_texels) (void)hipFree(c->env_texels);
     free_comms(c);
     if (c->gather) (void)hipFree(c->gather);
@@ -315,8 +349,10 @@ bool params_ok(const frt_render_params *p)
     if ((int64_t)p->nx * p->ny > (int64_t)INT32_MAX) return false;   // pixel indices are int32 (frt_shard_slots)
     if (p->flags & kRetiredFlags) return false;         // removed A/B plans: fail loudly, not silently
     if (p->integrator == FRT_INTEGRATOR_PATH || p->integrator == FRT_INTEGRATOR_AO ||
-        p->integrator == FRT_INTEGRATOR_NORMALS)
+        p->integrator == FRT_INTEGRATOR_NORMALS || p->integrator == FRT_INTEGRATOR_ALBEDO ||
+        p->integrator == FRT_INTEGRATOR_DEPTH)
         return true;
+    if (p->integrator == FRT_INTEGRATOR_DENOISE) return p->shard_count == 1;   // the stencil crosses tiles
     return p->integrator == FRT_INTEGRATOR_PSSMLT && p->mlt_chains > 0 && p->mlt_bootstrap > 0 &&
            p->sample_offset == 0;
 }
@@ -367,6 +403,8 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
 static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64, bool env_sampling)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
+    if (integrator == FRT_INTEGRATOR_ALBEDO || integrator == FRT_INTEGRATOR_DEPTH)   // no estimator flag, no image
+        return frt_feat::pick(c, integrator, flags, L);
     if ((flags & FRT_FLAG_SOBOL) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsSobol kernels, the roulette kernels' plans
         const bool rl = (flags & FRT_FLAG_ROULETTE) != 0;
         if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
@@ -760,13 +798,65 @@ extern "C" int frt_internal_work_granule(int integrator, int spp, int64_t n_slot
     return FRT_OK;
 }
 
+// FRT_INTEGRATOR_DENOISE: dev_slots holds the colour of the whole frame in slot
+// order.  The three feature films are the public renders of the same parameters
+// (this function again, one integrator each), into the context's feature
+// buffer; then the filter (frt_denoise.hip) rewrites the colour in place.
+static int render_denoise(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
+{
+    const auto t_start = std::chrono::steady_clock::now();
+    const int T = eff_tile(p);
+    const uint64_t n_slots64 = (uint64_t)(((p->nx + T - 1) / T) * (uint64_t)((p->ny + T - 1) / T)) * T * T;
+    if (n_slots64 >= 0xffffffffULL) return set_err(c, FRT_E_UNSUPPORTED, "frame too large for one call");
+    const uint32_t n_slots = (uint32_t)n_slots64;
+    const size_t plane = (size_t)n_slots * 3;
+    const size_t fbytes = std::max<size_t>(3 * plane * sizeof(float), 16);
+    if (fbytes > c->dn_feat_bytes) {
+        if (c->dn_feat) HIPCHK(c, hipFree(c->dn_feat));
+        c->dn_feat = nullptr;
+        c->dn_feat_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->dn_feat, fbytes));
+        c->dn_feat_bytes = fbytes;
+    }
+    const int kinds[3] = {FRT_INTEGRATOR_NORMALS, FRT_INTEGRATOR_DEPTH, FRT_INTEGRATOR_ALBEDO};   // albedo last: its plan fields stay
+    float *films[3] = {c->dn_feat, c->dn_feat + 2 * plane, c->dn_feat + plane};
+    frt_stats sum{};
+    for (int k = 0; k < 3; ++k) {
+        frt_render_params q = *p;
+        q.integrator = kinds[k];
+        frt_stats s{};
+        const int rc = render_impl(c, &q, films[k], st, &s);
+        if (rc != FRT_OK) return rc;
+        const frt_stats prev = sum;
+        sum = s;
+        sum.camera_rays += prev.camera_rays; sum.extension_rays += prev.extension_rays;
+        sum.shadow_rays += prev.shadow_rays; sum.samples += prev.samples; sum.work_items += prev.work_items;
+        sum.kernel_ms += prev.kernel_ms;
+    }
+    float ms = 0.0f;
+    const int rc = frt_denoise::run(c, p, dev_slots, films[0], films[2], films[1], n_slots, st, &ms);
+    if (rc != FRT_OK) return rc;
+    if (stats) {
+        *stats = sum;
+        stats->kernel_ms += ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return FRT_OK;
+}
+
 int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
 {
     const auto t_start = std::chrono::steady_clock::now();
     if (!c || !p) return FRT_E_INVALID;
-    if (!params_ok(p)) return set_err(c, FRT_E_INVALID, "bad render params");
+    if (!params_ok(p)) {
+        if (p->integrator == FRT_INTEGRATOR_DENOISE && p->shard_count != 1)
+            return set_err(c, FRT_E_INVALID, "denoise: shard_count must be 1 (the filter's stencil crosses tiles); "
+                                             "filter the assembled frame");
+        return set_err(c, FRT_E_INVALID, "bad render params");
+    }
     if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
     HIPCHK(c, hipSetDevice(c->device));
+    if (p->integrator == FRT_INTEGRATOR_DENOISE) return render_denoise(c, p, dev_slots, st, stats);
     c->mlt_rows = 0;                                   // `partial` is about to be reused
     if (p->integrator == FRT_INTEGRATOR_PSSMLT) {
         if (p->flags & FRT_FLAG_SOBOL)
@@ -857,8 +947,13 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("path_megakernel launch: ") + hipGetErrorString(le));
     HIPCHK(c, hipEventRecord(c->ev1, st));
     if (n_slots > 0) {
-        hipLaunchKernelGGL(film_reduce, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial, dev_slots, n_slots,
-                           n_chunks, p->spp, T, W.ntx, p->shard_index, p->shard_count, p->nx, p->ny);
+        if (p->integrator == FRT_INTEGRATOR_ALBEDO || p->integrator == FRT_INTEGRATOR_DEPTH)
+            hipLaunchKernelGGL(film_reduce_mean, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial, dev_slots,
+                               n_slots, n_chunks, p->spp, T, W.ntx, p->shard_index, p->shard_count, p->nx, p->ny,
+                               p->integrator == FRT_INTEGRATOR_DEPTH ? 1 : 0);
+        else
+            hipLaunchKernelGGL(film_reduce, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial, dev_slots, n_slots,
+                               n_chunks, p->spp, T, W.ntx, p->shard_index, p->shard_count, p->nx, p->ny);
         HIPCHK(c, hipGetLastError());
     }
     std::vector<unsigned long long> wr(n_waves * 4);
@@ -904,7 +999,16 @@ extern "C" int frt_render_device(frt_ctx *c, const frt_render_params *p, float *
 extern "C" int frt_render(frt_ctx *c, const frt_render_params *p, float *film_rgb, frt_stats *st)
 {
     if (!c || !film_rgb) return FRT_E_INVALID;
-    if (!params_ok(p)) return set_err(c, FRT_E_INVALID, "bad render params");
+    if (!params_ok(p)) return render_impl(c, p, nullptr, c->stream, st);   // its text for the refusal
+    const bool denoise = p->integrator == FRT_INTEGRATOR_DENOISE;
+    if (denoise) {   // the film is the input: refuse what the filter's weights are not defined for
+        if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+        const size_t n = (size_t)p->nx * p->ny * 3;
+        for (size_t i = 0; i < n; ++i)
+            if (!(film_rgb[i] >= 0.0f && film_rgb[i] <= FLT_MAX))
+                return set_err(c, FRT_E_INVALID, "denoise: film value " + std::to_string(film_rgb[i]) + " at pixel " +
+                                                     std::to_string(i / 3) + ": the colour must be finite and >= 0");
+    }
     const int64_t ns = frt_shard_slot_count(p);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = std::max<size_t>((size_t)ns * 3 * sizeof(float), 16);
@@ -914,10 +1018,16 @@ extern "C" int frt_render(frt_ctx *c, const frt_render_params *p, float *film_rg
         HIPCHK(c, hipMalloc(&c->slots_out, bytes));
         c->slots_out_bytes = bytes;
     }
-    const int rc = render_impl(c, p, c->slots_out, c->stream, st);
-    if (rc != FRT_OK) return rc;
     std::vector<float> host((size_t)ns * 3);
     std::vector<int32_t> map((size_t)ns);
+    if (denoise) {   // the colour, in slot order (padding slots: 0)
+        frt_shard_slots(p, map.data());
+        for (int64_t s = 0; s < ns; ++s)
+            for (int k = 0; k < 3; ++k) host[3 * s + k] = map[s] < 0 ? 0.0f : film_rgb[3 * (size_t)map[s] + k];
+        HIPCHK(c, hipMemcpy(c->slots_out, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const int rc = render_impl(c, p, c->slots_out, c->stream, st);
+    if (rc != FRT_OK) return rc;
     HIPCHK(c, hipMemcpy(host.data(), c->slots_out, host.size() * sizeof(float), hipMemcpyDeviceToHost));
     if (p->integrator == FRT_INTEGRATOR_PSSMLT) {   // splat film of this shard: accumulate
         for (size_t i = 0; i < host.size(); ++i) film_rgb[i] += host[i];

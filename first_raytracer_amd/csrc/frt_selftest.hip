@@ -41,11 +41,20 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
                 n_ext = n_sh = 0;
                 const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade<MATS>(P, S, h, n_sh)
                                   : p->integrator == FRT_INTEGRATOR_NORMALS ? normals_shade<MATS>(P, S, h)
+                                  : p->integrator == FRT_INTEGRATOR_ALBEDO ? albedo_shade(P, S, h)
+                                  : p->integrator == FRT_INTEGRATOR_DEPTH ? depth_shade(P, S, h)
                                   : path_shade<MATS>(P, S, h, p->max_depth, n_ext, n_sh);
                 cnt[1] += n_ext; cnt[2] += n_sh;
                 if (done) break;
             }
             acc = acc + P.L;
+        }
+        if (p->integrator == FRT_INTEGRATOR_ALBEDO || p->integrator == FRT_INTEGRATOR_DEPTH) {   // film_reduce_mean
+            const R n = (R)p->spp;
+            out_rgb[3 * i] = (float)(acc.x / n); out_rgb[3 * i + 1] = (float)(acc.y / n); out_rgb[3 * i + 2] = (float)(acc.z / n);
+            if (p->integrator == FRT_INTEGRATOR_DEPTH)
+                out_rgb[3 * i + 1] = depth_moment_floor(out_rgb[3 * i], out_rgb[3 * i + 1], out_rgb[3 * i + 2]);
+            continue;
         }
         const R k = R(1) / (R)p->spp;
         out_rgb[3 * i] = (float)(acc.x * k); out_rgb[3 * i + 1] = (float)(acc.y * k); out_rgb[3 * i + 2] = (float)(acc.z * k);
@@ -68,7 +77,11 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
     if (!sv || !p || !pixels || !out_rgb || npix < 0 || p->spp <= 0 || p->nx <= 0 || p->ny <= 0) return FRT_E_INVALID;
     for (int i = 0; i < npix; ++i)
         if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
-    const bool f64 = (p->flags & FRT_FLAG_FP64) != 0;
+    if (p->integrator == FRT_INTEGRATOR_DENOISE) return FRT_E_INVALID;   // a filter over a frame: no per-pixel code
+    // albedo, depth: fp32 and the hash stream whatever the flags say, and no environment
+    const bool feature = p->integrator == FRT_INTEGRATOR_ALBEDO || p->integrator == FRT_INTEGRATOR_DEPTH;
+    if (feature) env = nullptr;
+    const bool f64 = (p->flags & FRT_FLAG_FP64) != 0 && !feature;
     FlatScene F;
     std::string err;
     const int rc = flatten_scene(sv, F, err, f64);

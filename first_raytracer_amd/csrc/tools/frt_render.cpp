@@ -3,11 +3,17 @@
 // compile-time choices.  Writes the linear film as PFM (image.h:89-118).
 //
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
-//              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals] [--chains 262144]
+//              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals|albedo|depth] [--chains 262144]
+//              [--denoise [--denoise-spp 16]]
 //              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
+// --integrator albedo / depth: the first-hit feature images (FRT_INTEGRATOR_ALBEDO / _DEPTH, frt.h):
+//   reflectance colour; (depth x coverage, its second moment, coverage).
+// --denoise: after the last pass of a path or pssmlt render, filter the film (FRT_INTEGRATOR_DENOISE:
+//   an a-trous wavelet filter guided by --denoise-spp samples of normals, albedo and depth, on the
+//   first GPU) before --out / --png are written; prints the feature and filter times.
 // --env: constant environment colour (the reference scenes' is black).
 // --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
 //   image_texture, material.h:206-244); exclusive with --env.
@@ -26,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "frt_integrator.hpp"
 
@@ -36,7 +43,8 @@ int main(int argc, char **argv)
     long ns = 100;
     unsigned seed = 0;
     double env[3] = {0, 0, 0};
-    bool has_env = false, env_sampling = false, roulette = false, sobol = false;
+    bool has_env = false, env_sampling = false, roulette = false, sobol = false, denoise = false;
+    int denoise_spp = 16;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -62,6 +70,8 @@ int main(int argc, char **argv)
         else if (a == "--env-sampling") env_sampling = true;
         else if (a == "--roulette") roulette = true;
         else if (a == "--sobol") sobol = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-spp") denoise_spp = std::atoi(next());
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -77,6 +87,10 @@ int main(int argc, char **argv)
     }
     if (sobol && integrator != "path") {
         std::fprintf(stderr, "--sobol: only --integrator path draws Sobol' sample points\n");
+        return 2;
+    }
+    if (denoise && integrator != "path" && integrator != "pssmlt") {
+        std::fprintf(stderr, "--denoise: only a path or pssmlt film is filtered\n");
         return 2;
     }
     try {
@@ -112,9 +126,24 @@ int main(int argc, char **argv)
         } else if (integrator == "normals") {
             frt::renderer<frt::normals_gpu> render;
             run(render);
+        } else if (integrator == "albedo") {
+            frt::renderer<frt::albedo_gpu> render;
+            run(render);
+        } else if (integrator == "depth") {
+            frt::renderer<frt::depth_gpu> render;
+            run(render);
         } else {
             std::fprintf(stderr, "unknown integrator %s\n", integrator.c_str());
             return 2;
+        }
+        if (denoise) {   // the finished film, on the first GPU
+            std::vector<float> rgb(film.fout_image.begin(), film.fout_image.end());
+            for (float &v : rgb) v = v < 0.0f ? 0.0f : v;   // path sums can end a few 1e-6 below 0; the filter refuses negatives
+            frt::device_set gpu({0}, s.view(), s.env_map());
+            const frt_stats st = gpu.denoise(rgb.data(), nx, ny, denoise_spp, seed);
+            film.store_film(rgb.data());
+            std::printf("Denoised: %d-spp normals, albedo and depth and the filter took %.3f ms on the GPU (%.3f ms in all)\n",
+                        denoise_spp, st.kernel_ms, st.total_ms);
         }
         film.save_pfm(out);
         std::printf("Saved %s\n", out.c_str());

@@ -50,7 +50,49 @@ enum { FRT_DIST_GGX = 0, FRT_DIST_BECKMANN = 1 };   /* microfacet_distributions 
 enum { FRT_INTEGRATOR_PATH = 0,     /* path::Li           path.h:8-18, path.cpp:4-116      */
        FRT_INTEGRATOR_PSSMLT = 1,   /* pssmlt             pssmlt.h:29-76                   */
        FRT_INTEGRATOR_AO = 2,       /* ao::Li             ao.h:8-43, ao.cpp:4-27           */
-       FRT_INTEGRATOR_NORMALS = 3   /* normals_renderer   debug_renderer.h:6-50            */ };
+       FRT_INTEGRATOR_NORMALS = 3,  /* normals_renderer   debug_renderer.h:6-50            */
+       FRT_INTEGRATOR_ALBEDO = 4,   /* first-hit reflectance (below)                       */
+       FRT_INTEGRATOR_DEPTH = 5,    /* first-hit distance and coverage (below)             */
+       FRT_INTEGRATOR_DENOISE = 6   /* feature-guided filter of a finished film (below)    */ };
+/* FRT_INTEGRATOR_ALBEDO (not in the reference): the auxiliary image a compositor or
+ *   an external denoiser expects beside a low-sample render.  The film is the mean
+ *   over the pixel's samples of the reflectance colour at the camera ray's hit:
+ *   lambertian albedo (its checker or image texture applied at the hit, as path
+ *   sees it); modified_phong min(1, diffuse_reflectance (textured) + specular) per
+ *   channel; metal albedo; dielectric and rough_conductor specular (textured);
+ *   (1, 1, 1) on a diffuse_light and on a miss -- emitted and environment radiance
+ *   is not reflectance, and dividing by 1 leaves it alone.  Every value is in
+ *   [0, 1] for materials whose colours are.
+ * FRT_INTEGRATOR_DEPTH (not in the reference): per sample, t = the Euclidean
+ *   distance from the ray's origin (the lens point) to the hit; the film is
+ *   (mean of t hit, mean of t^2 hit, mean of hit) with hit = 1 / 0 -- mean depth
+ *   times coverage, its second moment, and coverage (alpha).  A miss adds
+ *   (0, 0, 0); coverage is exactly 1.0f where every sample hit, and the stored
+ *   floats keep y k >= x^2, so a variance taken from one film is never negative.
+ * Both: camera samples are path's (film and lens dimensions of the hash stream),
+ *   one camera ray a sample, no other ray; stats as normals.  They run in fp32
+ *   on the plans of normals, with sample_offset, shards, frt_render_multi and
+ *   every plan flag.  FRT_FLAG_FP64, _ENV_SAMPLING, _ROULETTE and _SOBOL have no
+ *   effect, max_depth is ignored, and neither reads the environment: a context
+ *   with an environment image runs the same kernels and gives the same film.
+ * FRT_INTEGRATOR_DENOISE: the film argument is input and output, the colour of
+ *   the whole frame (from path with any flags, accumulated progressive passes or
+ *   pssmlt): frt_render reads it in pixel order, frt_render_device in slot order
+ *   (padding slots stay as they are).  The call renders the normals, albedo and
+ *   depth films of the uploaded scene with spp samples each -- seed,
+ *   sample_offset, tile_size and the plan flags as given, bit-identical to the
+ *   public renders with the same parameters --, runs an edge-avoiding a-trous
+ *   wavelet filter (Dammertz et al. 2010; weights and constants: DESIGN.md
+ *   "Denoiser", csrc/frt_denoise.hpp) over the colour divided by the albedo,
+ *   multiplies the albedo back and writes the result over the film.
+ *   Ignored: max_depth, FRT_FLAG_ENV_SAMPLING / _ROULETTE / _SOBOL / _FP64.
+ *   Refused with FRT_E_INVALID and a text in frt_last_error: shard_count != 1
+ *   (the stencil crosses tiles); for frt_render a film value that is negative,
+ *   NaN or infinite, before any GPU work (frt_render_device does not look at
+ *   the contents); the per-pixel hooks frt_selftest_path_host[_env].
+ *   frt_render_multi runs the whole call on ctxs[0].  frt_stats: the sums of the
+ *   three feature passes, kernel_ms with the filter kernels, the plan fields of
+ *   the albedo pass. */
 enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes in HBM/L2 (A/B timing)  */
        FRT_FLAG_WAVES5 = 2,            /* register cap for 5 waves/SIMD (A/B timing)                     */
        FRT_FLAG_WAVES6 = 4,            /* register cap for 6 waves/SIMD (A/B timing)                     */

@@ -188,6 +188,20 @@ public:
     device_set &operator=(const device_set &) = delete;
     frt_ctx **data() { return ctx_.data(); }
     int size() const { return (int)ctx_.size(); }
+    // FRT_INTEGRATOR_DENOISE (frt.h) on the first context: filters the finished nx x ny colour
+    // film (finite, >= 0; from path, accumulated passes or pssmlt) in place, guided by spp-sample
+    // normals, albedo and depth renders of the uploaded scene.  Returns the call's stats.
+    frt_stats denoise(float *film_rgb, int nx, int ny, int spp = 16, uint32_t seed = 0, int tile_size = 32,
+                      int flags = 0)
+    {
+        if (ctx_.empty()) throw error(FRT_E_INVALID, "denoise: no device");
+        frt_render_params p{};
+        p.nx = nx; p.ny = ny; p.spp = spp; p.seed = seed; p.tile_size = tile_size; p.flags = flags;
+        p.integrator = FRT_INTEGRATOR_DENOISE; p.shard_index = 0; p.shard_count = 1;
+        frt_stats st{};
+        check(frt_render(ctx_[0], &p, film_rgb, &st), "frt_render(denoise)", ctx_[0]);
+        return st;
+    }
 
 private:
     void release()
@@ -248,6 +262,10 @@ struct tile_gpu {
 using path_gpu = tile_gpu<FRT_INTEGRATOR_PATH>;
 using ao_gpu = tile_gpu<FRT_INTEGRATOR_AO>;
 using normals_gpu = tile_gpu<FRT_INTEGRATOR_NORMALS>;
+// the first-hit feature images (not in the reference; frt.h): reflectance colour, and
+// (depth x coverage, its second moment, coverage); max_depth and the estimator switches do nothing
+using albedo_gpu = tile_gpu<FRT_INTEGRATOR_ALBEDO>;
+using depth_gpu = tile_gpu<FRT_INTEGRATOR_DEPTH>;
 
 // pssmlt_gpu: the drop-in for `pssmlt` (pssmlt.h:20-76) -- Kelemen PSS-MLT with
 // film->ns mutations per pixel over `chains` GPU chains (chain c -> device
