@@ -171,6 +171,16 @@ class Stats(ctypes.Structure):
         return d
 
 
+class TreeCost(ctypes.Structure):
+    """frt_tree_cost: a binary tree priced on the refinement pass's validation rays."""
+    _fields_ = [("v", ctypes.c_double), ("t", ctypes.c_double), ("j", ctypes.c_double), ("w", ctypes.c_double),
+                ("depth", ctypes.c_int32), ("n_nodes", ctypes.c_int32), ("n_rays", ctypes.c_int32),
+                ("applies", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class HostSceneInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n_tris", "n_spheres", "n_materials", "n_lights", "n_nodes",
                                               "world_kind", "n_list", "bvh_depth")] + [
@@ -191,6 +201,8 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_selftest_mlt_paths_host",
            "frt_set_env_image", "frt_scene_set_env_image", "frt_scene_env_image", "frt_read_hdr",
            "frt_selftest_path_host_env")
+# further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
+EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host")
 
 
 def lib():
@@ -259,6 +271,8 @@ def lib():
     L.frt_read_hdr.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), vp]
     L.frt_selftest_path_host_env.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp,
                                              ctypes.c_int, ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
+    L.frtx_selftest_tree_refine.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(TreeCost), vp, vp, ctypes.c_int32]
+    L.frtx_selftest_trace_host.argtypes = [ctypes.POINTER(SceneView), vp, ctypes.c_int64, vp]
     _lib = L
     return L
 
@@ -554,6 +568,32 @@ def selftest_path_host(scene, params, pixels, env_image=None):
                                             ctypes.byref(desc), out.ctypes.data, ctypes.byref(st)),
            "frt_selftest_path_host_env")
     return out, st
+
+
+def selftest_tree_refine(scene):
+    """Counting hook of the tree refinement pass (FRT_TREE_REFINE): the scene
+    flattened without and with the pass.  Returns ((cost_off, nodes_off),
+    (cost_on, nodes_on)): the TreeCost fields as a dict and the flattened node
+    records as an (n_nodes, 16) float32 array (child refs: columns 12, 13 viewed
+    as int32)."""
+    view = scene.view()
+    cap = max(1, view.n_tris + view.n_spheres)
+    nodes = [np.zeros((cap, 16), np.float32) for _ in range(2)]
+    out = (TreeCost * 2)()
+    _check(lib().frtx_selftest_tree_refine(ctypes.byref(view), out, nodes[0].ctypes.data, nodes[1].ctypes.data, cap),
+           "frtx_selftest_tree_refine")
+    return tuple((out[k].as_dict(), nodes[k][:out[k].n_nodes].copy()) for k in range(2))
+
+
+def selftest_trace_host(scene, rays):
+    """Context.trace_device's queries through the same code on the host: rays
+    (n, 8) float32 as for frt_trace_device -> hits (n, 4) float32."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    hits = np.zeros((len(rays), 4), np.float32)
+    view = scene.view()
+    _check(lib().frtx_selftest_trace_host(ctypes.byref(view), rays.ctypes.data, len(rays), hits.ctypes.data),
+           "frtx_selftest_trace_host")
+    return hits
 
 
 def selftest_mlt_paths_host(scene, nx, ny, seed, n):

@@ -1,6 +1,7 @@
 // frt_flatten.hip -- scene flattening on the host: DFS order, fp32 conversion
 // with outward-rounded boxes, multi-triangle leaves, the 4-wide quantized tree
-// (BVH4Q), the octant node copies and the texel conversion.  No kernel and no
+// (BVH4Q), the octant node copies, the texel conversion and the topology
+// refinement of LDS-resident trees (refine_tree).  No kernel and no
 // HIP runtime call; built with the kernel units' compiler and flags so that
 // its floating-point results do not depend on which unit holds it.
 #include "frt_flatten.hpp"
@@ -12,6 +13,7 @@
 #include <functional>
 
 #include "frt_kernels.hpp"   // the LDS budgets (kLdsSceneBytes, kLdsOctBytes, kLdsMaxDepth, oct_lds_node_slots)
+#include "host/tree_refine.hpp"
 
 using namespace frt;
 
@@ -285,7 +287,246 @@ int env_texels_of(const frt_image *img, std::vector<float4> &out, std::string &e
     return FRT_OK;
 }
 
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64)
+// octant copies of the binary nodes (when flatten_scene sized them): child boxes as (near xyz, far xyz)
+static void fill_octants(FlatScene &F)
+{
+    for (int o = 0; o < 8 && !F.nodes_oct.empty(); ++o)
+        for (size_t i = 0; i < F.nodes.size() / 4; ++i) {
+            const float4 *n = &F.nodes[4 * i];
+            const float b0[6] = {n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y};
+            const float b1[6] = {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w};
+            float q[12];
+            for (int a = 0; a < 3; ++a) {
+                const bool neg = (o >> a) & 1;
+                q[a] = neg ? b0[3 + a] : b0[a];
+                q[3 + a] = neg ? b0[a] : b0[3 + a];
+                q[6 + a] = neg ? b1[3 + a] : b1[a];
+                q[9 + a] = neg ? b1[a] : b1[3 + a];
+            }
+            float4 *d = &F.nodes_oct[(size_t)o * F.nodes.size() + 4 * i];
+            d[0] = make_float4(q[0], q[1], q[2], q[3]);
+            d[1] = make_float4(q[4], q[5], q[6], q[7]);
+            d[2] = make_float4(q[8], q[9], q[10], q[11]);
+            d[3] = n[3];
+        }
+}
+
+// ---- topology refinement of LDS-resident binary trees (DESIGN.md "Tree refinement") ----
+// The interior nodes above the leaves of collapse_leaves are rearranged to
+// lower the traversal cost J = V + w T (node visits and primitive tests per
+// ray) of the rays the scene's own path integrator traces: the surface area
+// heuristic prices rays uniform over the box, while these start on surfaces
+// inside the scene and a third of them are shadow rays to the lights.  Leaves,
+// their boxes and the device triangle ids (the DFS rank of the input tree) stay;
+// an interior box becomes the union of its children's padded fp32 boxes, which
+// bounds them.  The closest hit is the minimum of (t, device id) whatever the
+// visit order and a shadow ray asks only whether a hit exists (collapse_leaves,
+// trace_bvh), so every hit, film and ray count is unchanged -- only visits drop.
+//
+// kRefineW, the price of a primitive test in node visits: the VALU instructions
+// of one trip of leaf_hit's triangle loop over those of one node visit, both
+// read from the disassembly of the octant plan's path kernel (path_megakernel
+// <8, kWorldBvh2Oct, ...> of frt_render_lds.hip, the two innermost loops of
+// its step loop).  A node visit is 31: the record and ref addresses (2), 12
+// v_fma_f32, 8 v_maximum3 / v_minimum3, 4 compares, the select and store of
+// the far child (3), the select of the near one (1) and the loop test (1).  A
+// leaf trip whose triangle passes every stage of the Moller-Trumbore test --
+// in a wave, a trip where any lane does -- is 56: the determinant (12), u (11),
+// v (14), t and its interval (7), the hit update (8) and the loop count (4).
+// 56 / 31 = 1.8.
+constexpr double kRefineW = 1.8;
+// The ray samples: host replays of path::Li (path_begin / path_shade, the code the
+// kernel runs per lane) on a small frame of the scene's camera, one sample per
+// pixel, fixed seeds.  The search fits on the first and the result is judged on
+// the second, larger one, which it never saw.
+constexpr int kRefineFitFrame = 24, kRefineValFrame = 40;
+constexpr uint32_t kRefineFitSeed = 0x7ee5eed1u, kRefineValSeed = 0x7ee5eed2u;
+constexpr int kRefineMaxDepth = 33;      // the renders' default max_depth
+// Move evaluations per flatten, the pass's whole budget (no timer).  On Cornell
+// (19 leaves) the first sweep over every (subtree, place) pair takes ~600 and
+// finds all but a percent of the gain; 700 keep the pass under a frame's time
+// (0.17 s on one core against 0.23 s for the 1080p, 512 spp frame).
+constexpr int kRefineMaxEvals = 700;
+
+static bool tree_refine_knob()
+{
+    const char *e = std::getenv("FRT_TREE_REFINE");
+    return !(e && std::atoi(e) == 0);
+}
+
+// does the residency rule (frt_ctx.hpp pick_*) put this scene's binary tree in LDS?
+static bool tree_in_lds(const FlatScene &F)
+{
+    if (F.meta.world_kind != FRT_WORLD_BVH || F.meta.root < 0 || F.depth >= kLdsMaxDepth) return false;
+    const size_t bytes = sizeof(float4) * (F.nodes.size() + F.tris.size() + F.tshade.size() + F.mats.size());
+    return bytes <= kLdsSceneBytes || !F.nodes_oct.empty();
+}
+
+struct RefineLeaf { float box[6]; int ref; };   // lo xyz, hi xyz; the child ref as stored (~leaf)
+
+// the binary nodes as a topology over their leaves (interior node i = slot n_leaves + i)
+static void topology_of(const std::vector<float4> &nodes, frt_refine::Topology &t, std::vector<RefineLeaf> &leaves)
+{
+    const int nn = (int)(nodes.size() / 4);
+    leaves.clear();
+    t.child.assign(2 * (size_t)nn, 0);
+    t.n_leaves = nn + 1;
+    t.root = t.n_leaves;
+    for (int i = 0; i < nn; ++i) {
+        const float4 *n = &nodes[4 * i];
+        const float b[2][6] = {{n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y}, {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w}};
+        for (int side = 0; side < 2; ++side) {
+            const int c = f2i(side ? n[3].y : n[3].x);
+            if (c >= 0) { t.child[2 * i + side] = t.n_leaves + c; continue; }
+            RefineLeaf l;
+            for (int k = 0; k < 6; ++k) l.box[k] = b[side][k];
+            l.ref = c;
+            t.child[2 * i + side] = (int)leaves.size();
+            leaves.push_back(l);
+        }
+    }
+}
+
+// the rays of one replayed frame against the leaves
+static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leaves, int frame, uint32_t seed,
+                        frt_refine::RaySet &R)
+{
+    const DevScene S = host_scene(F);
+    struct Ray { f3 o, d; float tmax; bool shadow; };
+    std::vector<Ray> rays;
+    std::vector<int> stack(std::max(F.depth + 1, 1));
+    for (int pix = 0; pix < frame * frame; ++pix) {
+        PathState<float> P;
+        path_begin<kMatsAll>(P, S, pix % frame, pix / frame, frame, frame, seed, (uint32_t)pix, 0u);
+        for (;;) {
+            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow});
+            const Hit<float> h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+            uint32_t n_ext = 0, n_sh = 0;
+            if (path_shade<kMatsAll>(P, S, h, kRefineMaxDepth, n_ext, n_sh)) break;
+        }
+    }
+    const int n = (int)rays.size(), nl = (int)leaves.size();
+    R = frt_refine::RaySet{};
+    R.n = n;
+    R.n_leaves = nl;
+    R.prim_first.assign(nl + 1, 0);
+    for (int l = 0; l < nl; ++l) {
+        const int lref = ~leaves[l].ref;
+        const bool sph = (lref & FRT_PRIM_SPHERE) != 0;
+        const int first = sph ? lref : (lref & kLeafIndexMask), count = sph ? 1 : (lref >> kLeafCountShift) + 1;
+        for (int k = 0; k < count; ++k) R.prim_ref.push_back(first + k);
+        R.prim_first[l + 1] = (int)R.prim_ref.size();
+    }
+    R.n_prims = (int)R.prim_ref.size();
+    R.tmin.resize(n); R.tmax.resize(n); R.anyhit.resize(n); R.live.resize(n);
+    R.slab.resize((size_t)nl * n * 6);
+    R.prim_t.resize((size_t)n * R.n_prims);
+    // rays in a scattered order (a stride coprime to n), so that every chunk of the
+    // sample holds every part of the frame and every bounce
+    int stride = (int)(0.618 * n) | 1;
+    auto gcd = [](int a, int b) { while (b) { const int c = a % b; a = b; b = c; } return a; };
+    while (n > 1 && gcd(stride, n) != 1) stride += 2;
+    for (int i = 0; i < n; ++i) {
+        const Ray &q = rays[(int)(((int64_t)i * stride) % std::max(n, 1))];
+        Trav<float> T;
+        R.live[i] = trav_begin(T, S, S.root, q.o, q.d, q.tmax) ? 1 : 0;
+        R.tmin[i] = T.tmin;
+        R.tmax[i] = q.tmax;
+        R.anyhit[i] = q.shadow ? 1 : 0;
+        const float inv[3] = {T.sr.invd.x, T.sr.invd.y, T.sr.invd.z}, oi[3] = {T.sr.oinv.x, T.sr.oinv.y, T.sr.oinv.z};
+        for (int l = 0; l < nl; ++l) {
+            float *s = &R.slab[((size_t)i * nl + l) * 6];
+            for (int a = 0; a < 3; ++a) {
+                const bool neg = inv[a] < 0.0f;
+                s[a] = vfma(leaves[l].box[neg ? 3 + a : a], inv[a], oi[a]);
+                s[3 + a] = -vfma(leaves[l].box[neg ? a : 3 + a], inv[a], oi[a]);
+            }
+        }
+        for (int k = 0; k < R.n_prims; ++k) {
+            float u, v;
+            R.prim_t[(size_t)i * R.n_prims + k] = prim_t(S, R.prim_ref[k], q.o, q.d, T.tmin, q.tmax, u, v);
+        }
+    }
+}
+
+// F.nodes rewritten for topology t in pre-order: leaf boxes as they were, an
+// interior child's box the union of its children's
+static void write_topology(FlatScene &F, const frt_refine::Topology &t, const std::vector<RefineLeaf> &leaves)
+{
+    const int L = t.n_leaves, nn = L - 1;
+    std::vector<float> box(6 * (size_t)(L + nn));
+    std::function<void(int)> bound = [&](int s) {
+        float *b = &box[6 * (size_t)s];
+        if (s < L) { for (int k = 0; k < 6; ++k) b[k] = leaves[s].box[k]; return; }
+        const int c0 = t.child[2 * (s - L)], c1 = t.child[2 * (s - L) + 1];
+        bound(c0);
+        bound(c1);
+        for (int k = 0; k < 3; ++k) {
+            b[k] = std::min(box[6 * (size_t)c0 + k], box[6 * (size_t)c1 + k]);
+            b[3 + k] = std::max(box[6 * (size_t)c0 + 3 + k], box[6 * (size_t)c1 + 3 + k]);
+        }
+    };
+    bound(t.root);
+    std::vector<float4> out(4 * (size_t)nn);
+    int next = 0;
+    std::function<int(int)> emit = [&](int s) {   // returns the child ref of slot s
+        if (s < L) return leaves[s].ref;
+        const int me = next++;
+        const int c[2] = {t.child[2 * (s - L)], t.child[2 * (s - L) + 1]};
+        const float *a = &box[6 * (size_t)c[0]], *b = &box[6 * (size_t)c[1]];
+        out[4 * me + 0] = make_float4(a[0], a[1], a[2], a[3]);
+        out[4 * me + 1] = make_float4(a[4], a[5], b[0], b[1]);
+        out[4 * me + 2] = make_float4(b[2], b[3], b[4], b[5]);
+        const int r0 = emit(c[0]), r1 = emit(c[1]);
+        out[4 * me + 3] = make_float4(i2f(r0), i2f(r1), 0.0f, 0.0f);
+        return me;
+    };
+    emit(t.root);
+    F.nodes.swap(out);
+}
+
+bool tree_cost_host(const FlatScene &F, TreeCost &out)
+{
+    out = TreeCost{};
+    out.w = kRefineW;
+    if (!tree_in_lds(F) || F.nodes.empty()) return false;
+    frt_refine::Topology t;
+    std::vector<RefineLeaf> leaves;
+    topology_of(F.nodes, t, leaves);
+    frt_refine::RaySet val;
+    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, val);
+    const frt_refine::Cost c = frt_refine::tree_cost(t, val);
+    out.V = c.V; out.T = c.T; out.J = frt_refine::cost_j(c, kRefineW);
+    out.depth = t.depth();
+    out.n_rays = val.n;
+    return true;
+}
+
+// The pass itself, on a finished FlatScene.  True when F.nodes changed (the
+// caller makes the octant copies and BVH4Q again).  F.depth stays the input
+// tree's: the refined tree is never deeper, and the stack class and launch plan
+// chosen from it stay what they were.
+static bool refine_tree(FlatScene &F)
+{
+    if (!tree_in_lds(F) || F.nodes.size() / 4 < 3) return false;
+    frt_refine::Topology t;
+    std::vector<RefineLeaf> leaves;
+    topology_of(F.nodes, t, leaves);
+    const frt_refine::Topology input = t;
+    frt_refine::RaySet fit;
+    sample_rays(F, leaves, kRefineFitFrame, kRefineFitSeed, fit);
+    if (frt_refine::refine(t, fit, kRefineW, input.depth(), kRefineMaxEvals) == 0) return false;
+    // keep it only if the rays it was not fitted on agree
+    frt_refine::RaySet val;
+    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, val);
+    const double j0 = frt_refine::cost_j(frt_refine::tree_cost(input, val), kRefineW);
+    const double j1 = frt_refine::cost_j(frt_refine::tree_cost(t, val), kRefineW);
+    if (!(j1 < j0)) return false;
+    write_topology(F, t, leaves);
+    return true;
+}
+
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine)
 {
     auto fail = [&](int code, const std::string &m) { err = m; return code; };
     const int nt = sv->n_tris, ns = sv->n_spheres, nm = sv->n_materials;
@@ -548,29 +789,16 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
                                                F.tshade.size() + F.mats.size());
     if (sv->world_kind == FRT_WORLD_BVH && F.depth < kLdsMaxDepth && oct_bytes <= kLdsOctBytes)
         F.nodes_oct.resize(8 * F.nodes.size());
-    for (int o = 0; o < 8 && !F.nodes_oct.empty(); ++o)
-        for (size_t i = 0; i < F.nodes.size() / 4; ++i) {
-            const float4 *n = &F.nodes[4 * i];
-            const float b0[6] = {n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y};
-            const float b1[6] = {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w};
-            float q[12];
-            for (int a = 0; a < 3; ++a) {
-                const bool neg = (o >> a) & 1;
-                q[a] = neg ? b0[3 + a] : b0[a];
-                q[3 + a] = neg ? b0[a] : b0[3 + a];
-                q[6 + a] = neg ? b1[3 + a] : b1[a];
-                q[9 + a] = neg ? b1[a] : b1[3 + a];
-            }
-            float4 *d = &F.nodes_oct[(size_t)o * F.nodes.size() + 4 * i];
-            d[0] = make_float4(q[0], q[1], q[2], q[3]);
-            d[1] = make_float4(q[4], q[5], q[6], q[7]);
-            d[2] = make_float4(q[8], q[9], q[10], q[11]);
-            d[3] = n[3];
-        }
     S.root = (sv->world_kind == FRT_WORLD_BVH) ? ((sv->root >= 0) ? 0 : ~dev_ref(~sv->root)) : 0;
-    F.has4 = sv->world_kind == FRT_WORLD_BVH && build_bvh4(F, S.root);
-    if (!F.has4) F.nodes4.clear();
-    S.root4 = F.has4 ? F.root4 : S.root;
+    // the trees derived from the binary nodes: the octant copies and BVH4Q
+    auto derive_trees = [&]() {
+        fill_octants(F);
+        F.has4 = sv->world_kind == FRT_WORLD_BVH && build_bvh4(F, S.root);
+        if (!F.has4) F.nodes4.clear();
+        S.root4 = F.has4 ? F.root4 : S.root;
+        S.n_nodes4 = (int)(F.nodes4.size() / kNode4Parts);
+    };
+    derive_trees();
     S.n_lights = sv->n_lights;
     S.n_list = (int)F.list.size();
     S.n_nodes = (int)(F.nodes.size() / 4);
@@ -595,6 +823,9 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     S.cam64_h = d3d(sv->cam_horizontal); S.cam64_v = d3d(sv->cam_vertical);
     S.cam64_u = d3d(sv->cam_u); S.cam64_vv = d3d(sv->cam_v);
     S.lens_r64 = sv->cam_lens_radius;
+    // topology refinement (refine_tree): needs the finished scene for its ray sample, so the
+    // derived trees are made again from the nodes it rewrote
+    if ((refine < 0 ? tree_refine_knob() : refine != 0) && refine_tree(F)) derive_trees();
     return FRT_OK;
 }
 

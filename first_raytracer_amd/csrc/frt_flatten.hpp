@@ -27,7 +27,13 @@ struct FlatScene {
 };
 
 // f64: also build the fp64 records of the fp64 kernels (DESIGN.md "Precision")
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64);
+// refine: the topology refinement of LDS-resident binary trees; -1 = as FRT_TREE_REFINE says
+// (default on, read at each call), 0 = off, 1 = on
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1);
+// traversal cost of F's binary tree on the refinement pass's validation rays (the counting
+// self-test); false when the tree is not LDS-resident, so the pass does not apply
+struct TreeCost { double V = 0.0, T = 0.0, J = 0.0, w = 0.0; int depth = 0, n_rays = 0; };
+bool tree_cost_host(const FlatScene &F, TreeCost &out);
 // frt_set_env_image / the self-test: validate the image and convert it
 int env_texels_of(const frt_image *img, std::vector<float4> &out, std::string &err);
 // host image of the flattened scene as the kernels see it (HBM strides)

@@ -172,3 +172,53 @@ extern "C" int frt_selftest_mlt_paths_host(const frt_scene_view *sv, int nx, int
     }
     return FRT_OK;
 }
+
+// Counting hook of the tree refinement pass (frt_flatten.hip refine_tree): the
+// scene flattened without and with the pass, both trees priced on the pass's
+// validation rays, and the flattened node records for structure checks.
+extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost out[2], float *nodes_off,
+                                        float *nodes_on, int32_t max_nodes)
+{
+    if (!sv || !out) return FRT_E_INVALID;
+    float *dst[2] = {nodes_off, nodes_on};
+    for (int on = 0; on < 2; ++on) {
+        FlatScene F;
+        std::string err;
+        const int rc = flatten_scene(sv, F, err, false, on);
+        if (rc != FRT_OK) return rc;
+        TreeCost c;
+        const bool applies = tree_cost_host(F, c);
+        const int nn = (int)(F.nodes.size() / 4);
+        out[on] = frt_tree_cost{c.V, c.T, c.J, c.w, c.depth, nn, c.n_rays, applies ? 1 : 0};
+        if (dst[on]) {
+            if (nn > max_nodes) return FRT_E_INVALID;
+            memcpy(dst[on], F.nodes.data(), F.nodes.size() * sizeof(float4));
+        }
+    }
+    return FRT_OK;
+}
+
+// frt_trace_device's queries on the host: trace_bvh / trace_list over the scene flattened as an upload would
+extern "C" int frtx_selftest_trace_host(const frt_scene_view *sv, const float *rays, int64_t n, float *hits)
+{
+    if (!sv || n < 0 || (n > 0 && (!rays || !hits))) return FRT_E_INVALID;
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false);
+    if (rc != FRT_OK) return rc;
+    const DevScene S = host_scene(F);
+    std::vector<int> stack(std::max(F.depth + 1, 1));
+    for (int64_t i = 0; i < n; ++i) {
+        const float *q = rays + 8 * i;
+        const f3 o = mk3(q[0], q[1], q[2]), d = mk3(q[4], q[5], q[6]);
+        const bool anyhit = (f2i(q[7]) & 1) != 0;
+        const Hit<float> h = S.world_kind == FRT_WORLD_LIST ? trace<FRT_WORLD_LIST, 1>(S, o, d, q[3], anyhit, stack.data())
+                                                            : trace<FRT_WORLD_BVH, 1>(S, o, d, q[3], anyhit, stack.data());
+        const int ref = (h.prim < 0 || (h.prim & FRT_PRIM_SPHERE)) ? h.prim : F.tri_view[h.prim];
+        float *r = hits + 4 * i;
+        r[0] = h.t; r[1] = h.u; r[2] = h.v;
+        const float refbits = i2f(ref);
+        memcpy(&r[3], &refbits, sizeof(float));
+    }
+    return FRT_OK;
+}

@@ -535,6 +535,29 @@ int frt_selftest_path_host_env(const frt_scene_view *scene, const frt_render_par
 /* Same for PSS-MLT: n bootstrap-stream eye paths (frt_mlt.hpp) on the host;
  * out6 per path = film x, film y, r, g, b, scalar contribution. */
 int frt_selftest_mlt_paths_host(const frt_scene_view *scene, int nx, int ny, uint32_t seed, int n, float *out6);
+/* ---- frtx_*: further self-test hooks, added after the entry-point list of the
+ *      frt_* C-ABI was fixed (tests/abi_symbols.txt); the same calling rules,
+ *      a prefix of their own, no part of the drop-in boundary ---- */
+/* The counting hook of the tree refinement pass (FRT_TREE_REFINE, README): the
+ * scene is flattened without (out[0], nodes_off) and with (out[1], nodes_on)
+ * the pass, whatever the environment says, and both binary trees are priced on
+ * the pass's validation rays by the kernels' visit rule: v node visits and t
+ * primitive tests per ray, j = v + w t.  depth counts levels of interior
+ * nodes.  applies = 0: the tree is not LDS-resident, the pass does not run and
+ * nothing is priced (n_rays = 0).  nodes_*: n_nodes x 16 floats, the flattened
+ * node records (child 0 box lo hi, child 1 box lo hi, the two child refs as
+ * int32 bits, two unused); NULL to skip.  FRT_E_INVALID when n_nodes exceeds
+ * max_nodes. */
+typedef struct frt_tree_cost {
+    double v, t, j, w;
+    int32_t depth, n_nodes, n_rays, applies;
+} frt_tree_cost;
+int frtx_selftest_tree_refine(const frt_scene_view *scene, frt_tree_cost out[2], float *nodes_off, float *nodes_on,
+                             int32_t max_nodes);
+/* frt_trace_device's queries through the same code on the host (host memory,
+ * the same ray and hit layout), over the scene flattened as an upload would
+ * flatten it (FRT_TREE_REFINE and FRT_LEAF_SIZE are read) */
+int frtx_selftest_trace_host(const frt_scene_view *scene, const float *rays, int64_t n, float *hits);
 
 #ifdef __cplusplus
 }
