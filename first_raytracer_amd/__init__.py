@@ -42,6 +42,7 @@ FRT_GPU_BVH_SAH = 2
 FRT_INTEGRATOR_PATH, FRT_INTEGRATOR_PSSMLT, FRT_INTEGRATOR_AO, FRT_INTEGRATOR_NORMALS = 0, 1, 2, 3
 # first-hit feature images and the feature-guided film filter (frt.h; not in the reference)
 FRT_INTEGRATOR_ALBEDO, FRT_INTEGRATOR_DEPTH, FRT_INTEGRATOR_DENOISE = 4, 5, 6
+FRT_INTEGRATOR_ERROR = 8        # variance film of the context's last render (frt.h; 7 is not assigned)
 
 ERRORS = {0: "ok", -1: "invalid", -2: "hip", -3: "no scene", -4: "unsupported", -5: "io", -6: "no gfx950 device"}
 
@@ -139,7 +140,8 @@ class RenderParams(ctypes.Structure):
     def make(cls, nx, ny, spp, seed=0, max_depth=33, tile_size=32, shard_index=0, shard_count=1,
              samples_per_item=0, flags=0, integrator=0, sample_offset=0):
         """integrator: FRT_INTEGRATOR_PATH (path.cpp), _AO (ao.cpp), _NORMALS (debug_renderer.h),
-        _ALBEDO / _DEPTH (first-hit feature images) or _DENOISE (Context.denoise);
+        _ALBEDO / _DEPTH (first-hit feature images), _DENOISE (Context.denoise) or _ERROR
+        (Context.render_error);
         sample_offset: first global sample index (progressive passes)."""
         return cls(nx=nx, ny=ny, spp=spp, seed=seed, max_depth=max_depth, integrator=integrator, tile_size=tile_size,
                    shard_index=shard_index, shard_count=shard_count, samples_per_item=samples_per_item, flags=flags,
@@ -202,7 +204,7 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_set_env_image", "frt_scene_set_env_image", "frt_scene_env_image", "frt_read_hdr",
            "frt_selftest_path_host_env")
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
-EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host")
+EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance")
 
 
 def lib():
@@ -273,6 +275,7 @@ def lib():
                                              ctypes.c_int, ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
     L.frtx_selftest_tree_refine.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(TreeCost), vp, vp, ctypes.c_int32]
     L.frtx_selftest_trace_host.argtypes = [ctypes.POINTER(SceneView), vp, ctypes.c_int64, vp]
+    L.frtx_selftest_chunk_variance.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp]
     _lib = L
     return L
 
@@ -488,6 +491,31 @@ class Context:
                               integrator=FRT_INTEGRATOR_DENOISE)
         return self.render(p, film=film)
 
+    def render_error(self, params):
+        """FRT_INTEGRATOR_ERROR: the variance film V (ny, nx, 3) float32 of the film this context's
+        last render produced -- per pixel and channel the batch-means estimate of the variance of
+        the mean, from the spread of that render's chunk sums; sqrt(V) is the standard error.
+        params: that render's (nx, ny, spp, tile_size and the shard are compared).  Returns (V, stats)."""
+        p = RenderParams.from_buffer_copy(params)
+        p.integrator = FRT_INTEGRATOR_ERROR
+        return self.render(p)
+
+    def render_until(self, params, target, max_spp, first_spp=16):
+        """Progressive render of `params` (path or ao; spp and sample_offset are the driver's) that
+        stops at a requested error instead of a guessed sample count.  The frame figure is
+        e = sqrt(mean V) / mean film (frame_error): the predicted RMSE of the film over its mean.
+        Pass 0 renders first_spp samples (a power of two >= 2), each later pass as many as there
+        are so far; the film is accumulated with film_accumulate and V combined with
+        combine_variance (the passes are independent).  The loop ends when e <= target (converged)
+        or when the next pass would exceed max_spp.  With FRT_FLAG_SOBOL the samples of a pixel
+        are one net and V says nothing about its error: four replicates (seeds seed .. seed + 3)
+        are each extended by the same passes, the film is their mean and V the sample variance
+        of the four replicate means / 4 (replicate_variance); spp_used counts all four.
+        Returns (film, V, spp_used, e, converged)."""
+        film, V, spp, e, ok, _ = render_until(lambda p: self.render(p), lambda p: self.render_error(p)[0],
+                                              params, target, max_spp, first_spp)
+        return film, V, spp, e, ok
+
     def render_device(self, params, dev_ptr, stream_ptr=None):
         """Render this shard's slots into device memory at dev_ptr (slot_count*3 floats)."""
         st = Stats()
@@ -538,6 +566,106 @@ def render_multi(contexts, params, film=None):
     _check(lib().frt_render_multi(arr, len(contexts), ctypes.byref(params), film.ctypes.data, ctypes.byref(st)),
            "frt_render_multi", contexts[0].ptr)
     return film, st
+
+
+def frame_error(film, V):
+    """The frame figure of render_until: e = sqrt(mean V) / mean film, both means over all
+    3 nx ny values, in float64.  (frt::frame_error adds the same values one after the other:
+    the two agree to rounding, not bit for bit; the films of the two drivers do.)"""
+    f = np.asarray(film, np.float64)
+    v = np.asarray(V, np.float64)
+    return float(np.sqrt(v.sum() / v.size) / (f.sum() / f.size))
+
+
+def combine_variance(a, Va, b, Vb):
+    """Variance film of the mean of a + b samples from the variance films of the means of the
+    first a and the other b (independent passes): (a^2 Va + b^2 Vb) / (a + b)^2, in float64,
+    stored as float32."""
+    a, b = float(a), float(b)
+    va, vb = np.asarray(Va, np.float64), np.asarray(Vb, np.float64)
+    return (((a * a) * va + (b * b) * vb) / ((a + b) * (a + b))).astype(np.float32)
+
+
+def replicate_variance(films):
+    """(mean film float32, V float32) of four replicate films: V = the sample variance of the
+    four replicate means / 4, in float64 (np.var(films, axis=0, ddof=1) / 4); the mean film
+    through film_accumulate, one replicate at a time."""
+    assert len(films) == 4
+    r = [np.asarray(f, np.float64) for f in films]
+    m = (((r[0] + r[1]) + r[2]) + r[3]) * 0.25
+    v = ((((r[0] - m) ** 2 + (r[1] - m) ** 2) + (r[2] - m) ** 2) + (r[3] - m) ** 2) / 12.0
+    mean = np.array(films[0], np.float32, copy=True)
+    for k in range(1, 4):
+        mean = film_accumulate(mean, k, films[k], 1)
+    return mean, v.astype(np.float32)
+
+
+def render_until(render, render_error, params, target, max_spp, first_spp=16):
+    """The loop of Context.render_until over callables: render(params) -> (film, stats) and
+    render_error(params) -> V of the render just done.  Returns (film, V, spp_used, e,
+    converged, passes) with passes = [(spp_used, e, kernel ms of the pass)].
+    A pass whose render cut the samples into one chunk (stats.work_items equals the slot
+    count; the granule depends on the device, so it is seen only after the render) has no
+    spread to estimate from: it is rendered again with samples_per_item = half the pass --
+    that pass is paid twice -- and every later pass asks for half-pass granules up front."""
+    first_spp, max_spp = int(first_spp), int(max_spp)
+    if first_spp < 2 or first_spp & (first_spp - 1):
+        raise FrtError("render_until: first_spp must be a power of two >= 2")
+    if params.integrator not in (FRT_INTEGRATOR_PATH, FRT_INTEGRATOR_AO):
+        raise FrtError("render_until: path and ao renders only (pssmlt has no error estimate, denoise is a filter)")
+    if not target > 0:
+        raise FrtError("render_until: target must be > 0")
+    sobol = bool(params.flags & FRT_FLAG_SOBOL) and params.integrator == FRT_INTEGRATOR_PATH
+    reps = 4 if sobol else 1
+    if max_spp < reps * first_spp:
+        raise FrtError("render_until: max_spp is below the first pass")
+    slots = lib().frt_shard_slot_count(ctypes.byref(params))
+    if slots < 0:
+        raise FrtError("bad render params")
+    films, V, total, passes = [None] * reps, None, 0, []
+    halve = False
+    while True:
+        n = first_spp if total == 0 else total
+        ms = 0.0
+        for k in range(reps):
+            p = RenderParams.from_buffer_copy(params)
+            p.spp, p.sample_offset, p.seed = n, total, (params.seed + k) & 0xffffffff
+            if halve:
+                p.samples_per_item = n // 2
+            film, st = render(p)
+            if not sobol and st.work_items == slots:        # one chunk a pixel
+                halve = True
+                p.samples_per_item = n // 2
+                film, st = render(p)
+            ms += st.kernel_ms
+            if not sobol:
+                Vp = render_error(p)
+                V = Vp if total == 0 else combine_variance(total, V, n, Vp)
+            films[k] = film if total == 0 else film_accumulate(films[k], total, film, n)
+        total += n
+        if sobol:
+            film, V = replicate_variance(films)
+        else:
+            film = films[0]
+        e = frame_error(film, V)
+        passes.append((reps * total, e, ms))
+        if e <= target:
+            return film, V, reps * total, e, True, passes
+        if reps * 2 * total > max_spp:
+            return film, V, reps * total, e, False, passes
+
+
+def selftest_chunk_variance(partial, spp, spi):
+    """FRT_INTEGRATOR_ERROR's arithmetic on the host (frtx_selftest_chunk_variance): partial
+    (n_chunks, n_slots, 3) float32 chunk sums, chunks of spi samples, the last what is left of
+    spp -> V (n_slots, 3) float32."""
+    partial = np.ascontiguousarray(partial, dtype=np.float32)
+    k, n, three = partial.shape
+    assert three == 3
+    out = np.zeros((n, 3), np.float32)
+    _check(lib().frtx_selftest_chunk_variance(partial.ctypes.data, k, n, int(spp), int(spi), out.ctypes.data),
+           "frtx_selftest_chunk_variance")
+    return out
 
 
 def shard_slots(params):

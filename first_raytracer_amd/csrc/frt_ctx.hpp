@@ -44,6 +44,15 @@ struct frt_ctx {
     double last_mlt_b = 0.0;
     uint64_t mlt_rows = 0;        // chains whose state rows the last PSS-MLT render left in `partial`
     std::vector<void *> scene_bufs;
+    // FRT_INTEGRATOR_ERROR: what the last successful path / AO / normals / albedo / depth render
+    // left in `partial` -- the parameters an ERROR call must repeat and the granule it ran with.
+    // render_impl clears it before anything reuses `partial` and on every failure.
+    struct {
+        bool valid = false;
+        int nx = 0, ny = 0, spp = 0, tile = 0, shard_index = 0, shard_count = 0;
+        int spi = 0, n_chunks = 0;
+        uint32_t n_slots = 0;
+    } last_render;
     // workspace
     float *partial = nullptr; size_t partial_bytes = 0;
     unsigned *counter = nullptr;
@@ -115,5 +124,12 @@ void free_comms(frt_ctx *c);
 namespace frt_denoise {
 int run(frt_ctx *c, const frt_render_params *p, float *colour_slots, const float *normals_slots,
         const float *albedo_slots, const float *depth_slots, uint32_t n_slots, hipStream_t st, float *ms);
+}
+// frt_error.hip: the variance film of FRT_INTEGRATOR_ERROR in slot order (padding slots 0) from the
+// n_chunks x n_slots chunk sums in c->partial (chunks of spi samples, the last what is left of
+// p->spp); *ms gets the device time of its kernel
+namespace frt_error {
+int run(frt_ctx *c, const frt_render_params *p, float *out_slots, uint32_t n_slots, int n_chunks, int spi,
+        hipStream_t st, float *ms);
 }
 #pragma GCC visibility pop

@@ -89,6 +89,8 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
     for (int i = 0; i < n; ++i)
         if (!ctxs[i]) return FRT_E_INVALID;
     frt_ctx *c0 = ctxs[0];
+    if (p->integrator != FRT_INTEGRATOR_ERROR)   // a render that is refused or fails below leaves no record either
+        for (int i = 0; i < n; ++i) ctxs[i]->last_render.valid = false;
     if (!params_ok(p) || p->shard_count != 1 || p->shard_index != 0)
         return set_err(c0, FRT_E_INVALID, "frt_render_multi: params must describe the whole frame (shard 0 of 1)");
     // the filter's stencil crosses tiles, and its feature passes are a small part of a frame: one context

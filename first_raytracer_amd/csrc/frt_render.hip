@@ -350,7 +350,7 @@ bool params_ok(const frt_render_params *p)
     if (p->flags & kRetiredFlags) return false;         // removed A/B plans: fail loudly, not silently
     if (p->integrator == FRT_INTEGRATOR_PATH || p->integrator == FRT_INTEGRATOR_AO ||
         p->integrator == FRT_INTEGRATOR_NORMALS || p->integrator == FRT_INTEGRATOR_ALBEDO ||
-        p->integrator == FRT_INTEGRATOR_DEPTH)
+        p->integrator == FRT_INTEGRATOR_DEPTH || p->integrator == FRT_INTEGRATOR_ERROR)   // ERROR: the geometry of path
         return true;
     if (p->integrator == FRT_INTEGRATOR_DENOISE) return p->shard_count == 1;   // the stencil crosses tiles
     return p->integrator == FRT_INTEGRATOR_PSSMLT && p->mlt_chains > 0 && p->mlt_bootstrap > 0 &&
@@ -844,10 +844,53 @@ static int render_denoise(frt_ctx *c, const frt_render_params *p, float *dev_slo
     return FRT_OK;
 }
 
-int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
+// pixels of the frame that this shard's tiles hold
+static uint64_t shard_pixels(const frt_render_params *p)
+{
+    const int T = eff_tile(p), ntx = (p->nx + T - 1) / T, nmt = my_tiles(p);
+    uint64_t px = 0;
+    for (int t = 0; t < nmt; ++t) {
+        const int tile_id = p->shard_index + t * p->shard_count;
+        const int tx = tile_id % ntx, ty = tile_id / ntx;
+        px += (uint64_t)std::max(0, std::min(T, p->nx - tx * T)) * std::max(0, std::min(T, p->ny - ty * T));
+    }
+    return px;
+}
+
+// FRT_INTEGRATOR_ERROR: no ray is traced; the chunk sums that this context's last render left in
+// `partial` (c->last_render) are reduced to the variance film (frt_error.hip).  The record stays.
+static int render_error(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
 {
     const auto t_start = std::chrono::steady_clock::now();
-    if (!c || !p) return FRT_E_INVALID;
+    const auto &r = c->last_render;
+    if (!r.valid)
+        return set_err(c, FRT_E_INVALID, "error film: this context holds no chunk sums -- render path, ao, normals, albedo or "
+                                         "depth first (a pssmlt render, a denoise call and a failed render leave none)");
+    if (p->nx != r.nx || p->ny != r.ny || p->spp != r.spp || eff_tile(p) != r.tile || p->shard_index != r.shard_index ||
+        p->shard_count != r.shard_count)
+        return set_err(c, FRT_E_INVALID, "error film: nx, ny, spp, tile_size, shard_index and shard_count must be those of the "
+                                         "context's last render (" + std::to_string(r.nx) + " x " + std::to_string(r.ny) + ", " +
+                                         std::to_string(r.spp) + " spp, tile " + std::to_string(r.tile) + ", shard " +
+                                         std::to_string(r.shard_index) + " of " + std::to_string(r.shard_count) + ")");
+    if (r.n_chunks < 2)
+        return set_err(c, FRT_E_INVALID, "error film: the last render cut each pixel's samples into one chunk, which has no "
+                                         "spread; render with samples_per_item < spp (e.g. spp / 2) for more chunks");
+    float ms = 0.0f;
+    const int rc = frt_error::run(c, p, dev_slots, r.n_slots, r.n_chunks, r.spi, st, &ms);
+    if (rc != FRT_OK) return rc;
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->pixels = shard_pixels(p);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return FRT_OK;
+}
+
+// render_impl proper; the wrapper below keeps c->last_render
+static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
+{
+    const auto t_start = std::chrono::steady_clock::now();
     if (!params_ok(p)) {
         if (p->integrator == FRT_INTEGRATOR_DENOISE && p->shard_count != 1)
             return set_err(c, FRT_E_INVALID, "denoise: shard_count must be 1 (the filter's stencil crosses tiles); "
@@ -857,6 +900,7 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
     if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
     HIPCHK(c, hipSetDevice(c->device));
     if (p->integrator == FRT_INTEGRATOR_DENOISE) return render_denoise(c, p, dev_slots, st, stats);
+    if (p->integrator == FRT_INTEGRATOR_ERROR) return render_error(c, p, dev_slots, st, stats);
     c->mlt_rows = 0;                                   // `partial` is about to be reused
     if (p->integrator == FRT_INTEGRATOR_PSSMLT) {
         if (p->flags & FRT_FLAG_SOBOL)
@@ -970,13 +1014,7 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
             stats->camera_rays += wr[4 * w]; stats->extension_rays += wr[4 * w + 1];
             stats->shadow_rays += wr[4 * w + 2]; stats->samples += wr[4 * w + 3];
         }
-        uint64_t px = 0;
-        for (int t = 0; t < nmt; ++t) {
-            const int tile_id = p->shard_index + t * p->shard_count;
-            const int tx = tile_id % W.ntx, ty = tile_id / W.ntx;
-            px += (uint64_t)std::max(0, std::min(T, p->nx - tx * T)) * std::max(0, std::min(T, p->ny - ty * T));
-        }
-        stats->pixels = px;
+        stats->pixels = shard_pixels(p);
         stats->work_items = n_items;
         stats->scene_in_lds = L.lds_scene ? 1u : 0u;
         stats->waves_cap = (uint32_t)L.waves;
@@ -987,17 +1025,36 @@ int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStr
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
         stats->fp64 = L.f64 ? 1u : 0u;
     }
+    // the chunk sums of this render stay in `partial`: FRT_INTEGRATOR_ERROR reduces them
+    auto &r = c->last_render;
+    r.nx = p->nx; r.ny = p->ny; r.spp = p->spp; r.tile = T; r.shard_index = p->shard_index; r.shard_count = p->shard_count;
+    r.spi = spi; r.n_chunks = n_chunks; r.n_slots = n_slots;
+    r.valid = true;
     return FRT_OK;
+}
+
+// The record of FRT_INTEGRATOR_ERROR: every call but an ERROR call drops it first, so that a
+// failure, a pssmlt render (which reuses `partial`) and a denoise call (whose feature passes fill
+// it with other films) leave none; a render that fills `partial` sets it as its last step.
+int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
+{
+    if (!c || !p) return FRT_E_INVALID;
+    if (p->integrator != FRT_INTEGRATOR_ERROR) c->last_render.valid = false;
+    const int rc = render_impl_body(c, p, dev_slots, st, stats);
+    if (p->integrator == FRT_INTEGRATOR_DENOISE) c->last_render.valid = false;
+    return rc;
 }
 
 extern "C" int frt_render_device(frt_ctx *c, const frt_render_params *p, float *slots_rgb, void *hip_stream, frt_stats *st)
 {
+    if (c && p && p->integrator != FRT_INTEGRATOR_ERROR) c->last_render.valid = false;   // also where the call is refused below
     if (!c || !slots_rgb) return FRT_E_INVALID;
     return render_impl(c, p, slots_rgb, hip_stream ? (hipStream_t)hip_stream : c->stream, st);
 }
 
 extern "C" int frt_render(frt_ctx *c, const frt_render_params *p, float *film_rgb, frt_stats *st)
 {
+    if (c && p && p->integrator != FRT_INTEGRATOR_ERROR) c->last_render.valid = false;   // also where the call fails before render_impl
     if (!c || !film_rgb) return FRT_E_INVALID;
     if (!params_ok(p)) return render_impl(c, p, nullptr, c->stream, st);   // its text for the refusal
     const bool denoise = p->integrator == FRT_INTEGRATOR_DENOISE;

@@ -78,6 +78,7 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
     for (int i = 0; i < npix; ++i)
         if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
     if (p->integrator == FRT_INTEGRATOR_DENOISE) return FRT_E_INVALID;   // a filter over a frame: no per-pixel code
+    if (p->integrator == FRT_INTEGRATOR_ERROR) return FRT_E_INVALID;     // a reduction of a context's chunk sums: no per-pixel code
     // albedo, depth: fp32 and the hash stream whatever the flags say, and no environment
     const bool feature = p->integrator == FRT_INTEGRATOR_ALBEDO || p->integrator == FRT_INTEGRATOR_DEPTH;
     if (feature) env = nullptr;

@@ -5,6 +5,7 @@
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
 //              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals|albedo|depth] [--chains 262144]
 //              [--denoise [--denoise-spp 16]]
+//              [--error-out v.pfm] [--target-error E --max-spp N [--first-spp 16]]
 //              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
@@ -14,6 +15,12 @@
 // --denoise: after the last pass of a path or pssmlt render, filter the film (FRT_INTEGRATOR_DENOISE:
 //   an a-trous wavelet filter guided by --denoise-spp samples of normals, albedo and depth, on the
 //   first GPU) before --out / --png are written; prints the feature and filter times.
+// --error-out: also the variance film V of the render just done (FRT_INTEGRATOR_ERROR, frt.h: per
+//   pixel and channel the batch-means estimate of the variance of the mean), as PFM, and the frame
+//   figure e = sqrt(mean V) / mean film, the predicted RMSE over the mean; path and ao.
+// --target-error E --max-spp N: frt::render_until -- passes of --first-spp, then doubling, until
+//   e <= E or the next pass would exceed N samples per pixel; --ns is ignored; one line per pass
+//   with the total spp, e and the pass's kernel ms.  With --sobol four replicates give the error.
 // --env: constant environment colour (the reference scenes' is black).
 // --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
 //   image_texture, material.h:206-244); exclusive with --env.
@@ -45,6 +52,11 @@ int main(int argc, char **argv)
     double env[3] = {0, 0, 0};
     bool has_env = false, env_sampling = false, roulette = false, sobol = false, denoise = false;
     int denoise_spp = 16;
+    std::string error_out;
+    double target_error = 0.0;
+    long max_spp = 0;
+    int first_spp = 16;
+    bool has_target = false, has_max_spp = false, has_first_spp = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -72,6 +84,10 @@ int main(int argc, char **argv)
         else if (a == "--sobol") sobol = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-spp") denoise_spp = std::atoi(next());
+        else if (a == "--error-out") error_out = next();
+        else if (a == "--target-error") { target_error = std::atof(next()); has_target = true; }
+        else if (a == "--max-spp") { max_spp = std::atol(next()); has_max_spp = true; }
+        else if (a == "--first-spp") { first_spp = std::atoi(next()); has_first_spp = true; }
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -93,8 +109,21 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--denoise: only a path or pssmlt film is filtered\n");
         return 2;
     }
+    const bool until = has_target;
+    if (until && !(target_error > 0.0)) { std::fprintf(stderr, "--target-error must be > 0\n"); return 2; }
+    if (!until && (has_max_spp || has_first_spp)) {
+        std::fprintf(stderr, "--max-spp / --first-spp go with --target-error\n");
+        return 2;
+    }
+    if ((until || !error_out.empty()) && integrator != "path" && integrator != "ao") {
+        std::fprintf(stderr, "--error-out / --target-error: only a path or ao render has an error film\n");
+        return 2;
+    }
+    if (until && max_spp <= 0) { std::fprintf(stderr, "--target-error needs --max-spp\n"); return 2; }
+    if (until && denoise) { std::fprintf(stderr, "--target-error and --denoise exclude each other\n"); return 2; }
     try {
-        std::printf("Resolution: %dx%d\nSetting number of samples to %ld\n", nx, ny, ns);
+        if (until) std::printf("Resolution: %dx%d\nRendering until e <= %g, at most %ld samples\n", nx, ny, target_error, max_spp);
+        else std::printf("Resolution: %dx%d\nSetting number of samples to %ld\n", nx, ny, ns);
         const std::string kind = scene == "cornell" ? "cornell_box_obj" : scene == "veach" ? "veach_mis" : "obj_smooth";
         frt::Scene s(kind, obj, double(nx) / double(ny));
         if (has_env) s.set_env(env[0], env[1], env[2]);
@@ -104,11 +133,39 @@ int main(int argc, char **argv)
         std::printf("BVH construction took me %g seconds (%d triangles, depth %d).\n", s.info().build_ms * 1e-3,
                     s.info().n_tris, s.info().bvh_depth);
         frt::viewer film(nx, ny, (uint64_t)ns);
+        std::vector<float> variance;   // --error-out
+        auto report_error = [&](const std::vector<float> &rgb) {
+            std::printf("Error film: e = sqrt(mean V) / mean film = %.6g\n", frt::frame_error(rgb.data(), variance.data(), rgb.size()));
+        };
         auto run = [&](auto &render) {
             render.devices.clear();
             for (int g = 0; g < gpus; ++g) render.devices.push_back(g);
             render.seed = seed;
             render.Render(&s, film);
+        };
+        // path, ao: ... with the error film, or until converged
+        auto run_error = [&](auto &render) {
+            render.devices.clear();
+            for (int g = 0; g < gpus; ++g) render.devices.push_back(g);
+            render.seed = seed;
+            if (until) {
+                frt::device_set set(render.devices, s.view(), s.env_map());
+                const frt::until_result r = frt::render_until(set, render.params(nx, ny, first_spp), target_error, max_spp, first_spp,
+                                                              [](long spp, double e, double ms) {
+                                                                  std::printf("pass: %ld spp  e = %.6g  %.3f ms\n", spp, e, ms);
+                                                              });
+                std::printf("%s after %ld spp: e = %.6g (target %.6g)\n", r.converged ? "Converged" : "Not converged",
+                            r.spp_used, r.e, target_error);
+                film.store_film(r.film.data());
+                variance = r.variance;
+                return;
+            }
+            render.keep_devices = !error_out.empty();
+            render.Render(&s, film);
+            if (!error_out.empty()) {
+                variance = render.error();
+                report_error(std::vector<float>(film.fout_image.begin(), film.fout_image.end()));
+            }
         };
         if (integrator == "pssmlt") {
             frt::renderer<frt::pssmlt_gpu> render;
@@ -119,10 +176,12 @@ int main(int argc, char **argv)
             render.env_sampling = env_sampling;
             render.roulette = roulette;
             render.sobol = sobol;
-            run(render);
+            if (until || !error_out.empty()) run_error(render);
+            else run(render);
         } else if (integrator == "ao") {
             frt::renderer<frt::ao_gpu> render;
-            run(render);
+            if (until || !error_out.empty()) run_error(render);
+            else run(render);
         } else if (integrator == "normals") {
             frt::renderer<frt::normals_gpu> render;
             run(render);
@@ -147,6 +206,10 @@ int main(int argc, char **argv)
         }
         film.save_pfm(out);
         std::printf("Saved %s\n", out.c_str());
+        if (!error_out.empty()) {
+            frt::check(frt_write_pfm(error_out.c_str(), nx, ny, variance.data()), "frt_write_pfm");
+            std::printf("Saved %s\n", error_out.c_str());
+        }
         if (!png.empty()) {
             film.save_image(png, FRT_IMAGE_PNG);
             std::printf("Saved %s\n", png.c_str());

@@ -53,7 +53,9 @@ enum { FRT_INTEGRATOR_PATH = 0,     /* path::Li           path.h:8-18, path.cpp:
        FRT_INTEGRATOR_NORMALS = 3,  /* normals_renderer   debug_renderer.h:6-50            */
        FRT_INTEGRATOR_ALBEDO = 4,   /* first-hit reflectance (below)                       */
        FRT_INTEGRATOR_DEPTH = 5,    /* first-hit distance and coverage (below)             */
-       FRT_INTEGRATOR_DENOISE = 6   /* feature-guided filter of a finished film (below)    */ };
+       FRT_INTEGRATOR_DENOISE = 6,  /* feature-guided filter of a finished film (below)    */
+       /* 7: not assigned, FRT_E_INVALID */
+       FRT_INTEGRATOR_ERROR = 8     /* variance film of the context's last render (below)  */ };
 /* FRT_INTEGRATOR_ALBEDO (not in the reference): the auxiliary image a compositor or
  *   an external denoiser expects beside a low-sample render.  The film is the mean
  *   over the pixel's samples of the reflectance colour at the camera ray's hit:
@@ -92,7 +94,42 @@ enum { FRT_INTEGRATOR_PATH = 0,     /* path::Li           path.h:8-18, path.cpp:
  *   the contents); the per-pixel hooks frt_selftest_path_host[_env].
  *   frt_render_multi runs the whole call on ctxs[0].  frt_stats: the sums of the
  *   three feature passes, kernel_ms with the filter kernels, the plan fields of
- *   the albedo pass. */
+ *   the albedo pass.
+ * FRT_INTEGRATOR_ERROR (not in the reference): the per-pixel error estimate of the
+ *   film that this context's last successful render produced.  frt_render,
+ *   frt_render_device and frt_render_multi trace no ray: they reduce the partial
+ *   sums that render left on the device.  A render of kind path, ao, normals,
+ *   albedo or depth leaves them, on any plan, with any flags, in fp32 or fp64 (the
+ *   sums are fp32 in both).  It cut the samples of a pixel into K disjoint chunks
+ *   (samples_per_item samples each, the last one what is left; 0 = the library's
+ *   choice); with chunk c holding n_c samples with sum S_c, N = sum n_c,
+ *   m_c = S_c / n_c and m = sum S_c / N, the film is, per pixel and channel,
+ *       V = sum_c n_c (m_c - m)^2 / ((K - 1) N),
+ *   the batch-means estimate: for independent samples the unbiased estimate of
+ *   the variance of the pixel's mean, its square root the standard error.  fp32,
+ *   one pass, West's weighted incremental update (csrc/frt_error.hpp); every value
+ *   is finite and >= 0, and exactly 0 where all chunk means are bit-equal.
+ *   frt_render scatters V into pixel order (only this shard's pixels are written);
+ *   frt_render_device writes slot order, padding slots exactly 0.
+ *   nx, ny, spp, tile_size, shard_index and shard_count must equal the recorded
+ *   render's; every other field is ignored.  frt_render_multi hands shard (i, n)
+ *   to ctxs[i] as it does for renders, and each context reduces its own shard:
+ *   call it with the contexts, in the order, of the render.
+ *   Refused with FRT_E_INVALID and a text in frt_last_error: no recorded render,
+ *   or other parameters; a recorded render with K = 1 (render with
+ *   samples_per_item < spp); the per-pixel hooks frt_selftest_path_host[_env].
+ *   The record: a pssmlt render, a DENOISE call and any render call that fails
+ *   or is refused (one refused for a null pointer aside) clear it -- they reuse or
+ *   do not fill the sums --; frt_upload_scene, frt_set_env_image and
+ *   frt_trace_device do not; an ERROR call leaves it, so calls repeat bit for bit.
+ *   frt_stats: the ray counters, samples and work_items 0, pixels as for a render,
+ *   kernel_ms the reduce kernel's time.
+ *   FRT_FLAG_SOBOL: the call is accepted when the recorded render used the flag,
+ *   but the samples of a pixel are then one stratified net and not independent
+ *   draws: V estimates the variance of the unstratified estimator, an upper
+ *   estimate of the true error (render_until, include/frt_integrator.hpp, takes
+ *   its error from independent replicates in that case).
+ *   frt_shard_slot_count / frt_shard_slots: the geometry of path. */
 enum { FRT_FLAG_NO_LDS_SCENE = 1,      /* render_params.flags: keep small scenes in HBM/L2 (A/B timing)  */
        FRT_FLAG_WAVES5 = 2,            /* register cap for 5 waves/SIMD (A/B timing)                     */
        FRT_FLAG_WAVES6 = 4,            /* register cap for 6 waves/SIMD (A/B timing)                     */
@@ -558,6 +595,12 @@ int frtx_selftest_tree_refine(const frt_scene_view *scene, frt_tree_cost out[2],
  * the same ray and hit layout), over the scene flattened as an upload would
  * flatten it (FRT_TREE_REFINE and FRT_LEAF_SIZE are read) */
 int frtx_selftest_trace_host(const frt_scene_view *scene, const float *rays, int64_t n, float *hits);
+/* FRT_INTEGRATOR_ERROR's arithmetic (csrc/frt_error.hpp, the code the kernel runs per element) on
+ * host memory: partial = n_chunks x n_slots x 3 chunk sums in the device layout (slot s of chunk c
+ * at 3 (c n_slots + s)), chunks of spi samples, the last one spp - (n_chunks - 1) spi (1 .. spi);
+ * every slot is valid; out = n_slots x 3.  FRT_E_INVALID for n_chunks < 2 or counts that do not
+ * describe such a cut. */
+int frtx_selftest_chunk_variance(const float *partial, int n_chunks, int64_t n_slots, int spp, int spi, float *out);
 
 #ifdef __cplusplus
 }

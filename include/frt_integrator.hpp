@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -181,7 +182,7 @@ public:
         if (!devices.empty()) up(0);
         for (auto &t : th) t.join();
         for (const std::string &e : errs)
-            if (!e.empty()) { release(); throw error(FRT_E_HIP, e); }
+            if (!e.empty()) { release(); throw frt::error(FRT_E_HIP, e); }
     }
     ~device_set() { release(); }
     device_set(const device_set &) = delete;
@@ -194,12 +195,24 @@ public:
     frt_stats denoise(float *film_rgb, int nx, int ny, int spp = 16, uint32_t seed = 0, int tile_size = 32,
                       int flags = 0)
     {
-        if (ctx_.empty()) throw error(FRT_E_INVALID, "denoise: no device");
+        if (ctx_.empty()) throw frt::error(FRT_E_INVALID, "denoise: no device");
         frt_render_params p{};
         p.nx = nx; p.ny = ny; p.spp = spp; p.seed = seed; p.tile_size = tile_size; p.flags = flags;
         p.integrator = FRT_INTEGRATOR_DENOISE; p.shard_index = 0; p.shard_count = 1;
         frt_stats st{};
         check(frt_render(ctx_[0], &p, film_rgb, &st), "frt_render(denoise)", ctx_[0]);
+        return st;
+    }
+    // FRT_INTEGRATOR_ERROR (frt.h): the variance film V (nx x ny x 3, pixel order) of the film that
+    // the last frt_render_multi of these contexts with `p` produced -- per pixel and channel the
+    // batch-means estimate of the variance of the mean; sqrt(V) is the standard error.  No ray is
+    // traced; each context reduces the chunk sums of its own shard.  Returns the call's stats.
+    frt_stats error(frt_render_params p, float *v_rgb)
+    {
+        if (ctx_.empty()) throw frt::error(FRT_E_INVALID, "error: no device");
+        p.integrator = FRT_INTEGRATOR_ERROR; p.shard_index = 0; p.shard_count = 1;
+        frt_stats st{};
+        check(frt_render_multi(ctx_.data(), size(), &p, v_rgb, &st), "frt_render_multi(error)", ctx_[0]);
         return st;
     }
 
@@ -235,28 +248,54 @@ struct tile_gpu {
     // frt.h) -- not in the reference; the same expectation with less noise per sample; off by
     // default, on every device of `devices` when set; ao and normals ignore it
     bool sobol = false;
+    // keep the contexts of the last Render() until the next one (off: they are released when
+    // Render() returns, as before): error() needs the chunk sums they hold
+    bool keep_devices = false;
     frt_stats last_stats{};
     static constexpr bool using_custom_viewer = false;
 
-    void Render(Scene *scene, viewer *film)
+    // the whole-frame request of an nx x ny render with spp samples under this integrator's switches
+    frt_render_params params(int nx, int ny, int spp) const
     {
-        device_set gpus(devices, scene->view(), scene->env_map());
         frt_render_params p{};
-        p.nx = film->nx; p.ny = film->ny; p.spp = (int)film->ns; p.seed = seed;
+        p.nx = nx; p.ny = ny; p.spp = spp; p.seed = seed;
         p.max_depth = max_depth; p.integrator = INTEGRATOR; p.tile_size = tile_size;
         p.shard_index = 0; p.shard_count = 1;
         if (env_sampling) p.flags |= FRT_FLAG_ENV_SAMPLING;
         if (roulette) p.flags |= FRT_FLAG_ROULETTE;
         if (sobol) p.flags |= FRT_FLAG_SOBOL;
+        return p;
+    }
+
+    void Render(Scene *scene, viewer *film)
+    {
+        kept_.reset();
+        std::unique_ptr<device_set> owned(new device_set(devices, scene->view(), scene->env_map()));
+        device_set &gpus = *owned;
+        const frt_render_params p = params(film->nx, film->ny, (int)film->ns);
         std::vector<float> rgb((size_t)film->nx * film->ny * 3, 0.0f);
         check(frt_render_multi(gpus.data(), gpus.size(), &p, rgb.data(), &last_stats), "frt_render_multi",
               gpus.data()[0]);
+        if (keep_devices) { kept_ = std::move(owned); kept_params_ = p; }
         for (int y = 0; y < film->ny; ++y)
             for (int x = 0; x < film->nx; ++x) {
                 const float *px = &rgb[3 * ((size_t)y * film->nx + x)];
                 film->store_mean(x, y, px[0], px[1], px[2]);
             }
     }
+    // The variance film of the last Render() (FRT_INTEGRATOR_ERROR, device_set::error): nx x ny x 3
+    // floats in the film's order.  Needs keep_devices = true before that Render().
+    std::vector<float> error()
+    {
+        if (!kept_) throw frt::error(FRT_E_INVALID, "error(): set keep_devices before Render()");
+        std::vector<float> v((size_t)kept_params_.nx * kept_params_.ny * 3, 0.0f);
+        kept_->error(kept_params_, v.data());
+        return v;
+    }
+
+private:
+    std::unique_ptr<device_set> kept_;
+    frt_render_params kept_params_{};
 };
 
 using path_gpu = tile_gpu<FRT_INTEGRATOR_PATH>;
@@ -295,6 +334,112 @@ struct pssmlt_gpu {
             }
     }
 };
+
+// ---- render until converged (not in the reference, whose ns is a compile-time guess) ----
+// The frame figure e = sqrt(mean V) / mean film, both means over all n = 3 nx ny values: the
+// predicted RMSE of the film over its mean.  (The binding's frame_error adds the same values in
+// numpy's pairwise order: the two agree to rounding, not bit for bit; the films do.)
+inline double frame_error(const float *film, const float *v, size_t n)
+{
+    double sf = 0.0, sv = 0.0;
+    for (size_t i = 0; i < n; ++i) { sf += (double)film[i]; sv += (double)v[i]; }
+    return std::sqrt(sv / (double)n) / (sf / (double)n);
+}
+// V of the mean of a + b samples from the V of the first a (in place) and of the other b, the
+// passes independent: (a^2 Va + b^2 Vb) / (a + b)^2 in double, stored as float
+inline void combine_variance(float *v, long a, const float *vp, long b, size_t n)
+{
+    const double da = (double)a, db = (double)b;
+    const double wa = da * da, wb = db * db, tot = (da + db) * (da + db);
+    for (size_t i = 0; i < n; ++i) v[i] = (float)((wa * (double)v[i] + wb * (double)vp[i]) / tot);
+}
+// four replicate films -> their mean (through frt_film_accumulate, one replicate at a time) and
+// V = the sample variance of the four replicate means / 4
+inline void replicate_variance(const std::vector<float> r[4], std::vector<float> &mean, std::vector<float> &v)
+{
+    const size_t n = r[0].size();
+    mean = r[0];
+    for (int k = 1; k < 4; ++k) check(frt_film_accumulate(mean.data(), k, r[k].data(), 1, (int64_t)n), "frt_film_accumulate");
+    v.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double a = r[0][i], b = r[1][i], c = r[2][i], d = r[3][i];
+        const double m = (((a + b) + c) + d) * 0.25;
+        v[i] = (float)(((((a - m) * (a - m) + (b - m) * (b - m)) + (c - m) * (c - m)) + (d - m) * (d - m)) / 12.0);
+    }
+}
+
+struct until_result {
+    std::vector<float> film, variance;   // nx x ny x 3 each, the film's order
+    long spp_used = 0;
+    double e = 0.0;
+    bool converged = false;
+};
+
+// Progressive render of the whole-frame request `p` (path or ao; spp and sample_offset are the
+// driver's) on `gpus` until e <= target or the next pass would exceed max_spp.  Pass 0 renders
+// first_spp samples (a power of two >= 2), each later pass as many as there are so far
+// (sample_offset = the total so far); the film is accumulated with frt_film_accumulate and V, the
+// ERROR film of each pass, with combine_variance.  A pass that the library cut into one chunk a
+// pixel (work_items == the slot count; the granule depends on the device, so it is seen only
+// after the render) is rendered again with samples_per_item = half the pass -- that pass is paid
+// twice -- and every later pass asks for half-pass granules up front.
+// FRT_FLAG_SOBOL: four replicates, seeds seed .. seed + 3, each extended by the same passes (so
+// each stays a prefix net); film and V from replicate_variance, spp_used counts all four, and the
+// ERROR integrator is not called.  on_pass(total spp, e, kernel ms of the pass) after every pass.
+// The loop of the Python binding's Context.render_until, film for film.
+inline until_result render_until(device_set &gpus, frt_render_params p, double target, long max_spp, int first_spp = 16,
+                                 const std::function<void(long, double, double)> &on_pass = nullptr)
+{
+    if (first_spp < 2 || (first_spp & (first_spp - 1))) throw error(FRT_E_INVALID, "render_until: first_spp must be a power of two >= 2");
+    if (p.integrator != FRT_INTEGRATOR_PATH && p.integrator != FRT_INTEGRATOR_AO)
+        throw error(FRT_E_INVALID, "render_until: path and ao renders only (pssmlt has no error estimate, denoise is a filter)");
+    if (!(target > 0.0)) throw error(FRT_E_INVALID, "render_until: target must be > 0");
+    const bool sobol = (p.flags & FRT_FLAG_SOBOL) && p.integrator == FRT_INTEGRATOR_PATH;
+    const int reps = sobol ? 4 : 1;
+    if (max_spp < (long)reps * first_spp) throw error(FRT_E_INVALID, "render_until: max_spp is below the first pass");
+    p.shard_index = 0; p.shard_count = 1;
+    const int64_t slots = frt_shard_slot_count(&p);
+    if (slots < 0) throw error(FRT_E_INVALID, "render_until: bad render params");
+    const size_t n3 = (size_t)p.nx * p.ny * 3;
+    std::vector<float> films[4], pass(n3), vp(n3);
+    until_result R;
+    long total = 0;
+    bool halve = false;   // a pass came out as one chunk: the later ones ask for two
+    for (;;) {
+        const long n = total == 0 ? first_spp : total;
+        double ms = 0.0;
+        for (int k = 0; k < reps; ++k) {
+            frt_render_params q = p;
+            q.spp = (int)n; q.sample_offset = (int)total; q.seed = p.seed + (uint32_t)k;
+            if (halve) q.samples_per_item = (int)(n / 2);
+            frt_stats st{};
+            check(frt_render_multi(gpus.data(), gpus.size(), &q, pass.data(), &st), "frt_render_multi", gpus.data()[0]);
+            if (!sobol && st.work_items == (uint64_t)slots) {   // one chunk a pixel
+                halve = true;
+                q.samples_per_item = (int)(n / 2);
+                check(frt_render_multi(gpus.data(), gpus.size(), &q, pass.data(), &st), "frt_render_multi", gpus.data()[0]);
+            }
+            ms += st.kernel_ms;
+            if (!sobol) {
+                gpus.error(q, vp.data());
+                if (total == 0) R.variance = vp;
+                else combine_variance(R.variance.data(), total, vp.data(), n, n3);
+            }
+            if (total == 0) films[k] = pass;
+            else check(frt_film_accumulate(films[k].data(), total, pass.data(), n, (int64_t)n3), "frt_film_accumulate");
+        }
+        total += n;
+        if (sobol) replicate_variance(films, R.film, R.variance);
+        R.spp_used = reps * total;
+        const std::vector<float> &film = sobol ? R.film : films[0];
+        R.e = frame_error(film.data(), R.variance.data(), n3);
+        if (on_pass) on_pass(R.spp_used, R.e, ms);
+        R.converged = R.e <= target;
+        if (R.converged || 2 * R.spp_used > max_spp) break;
+    }
+    if (!sobol) R.film = films[0];
+    return R;
+}
 
 // renderer<I> (integrator.h:11-47): time I::Render, print the statistics the
 // reference prints -- with true 64-bit ray counts instead of node visits.
