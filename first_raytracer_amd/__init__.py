@@ -183,6 +183,21 @@ class TreeCost(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PlanQuery(ctypes.Structure):
+    """frt_plan_query: the scene properties and the call whose launch plan selftest_plan asks for."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "integrator", "flags", "world_kind", "stack_needed", "has_bvh4",
+                                              "depth4", "mats", "has_spec_mats", "env_image", "env_sampling",
+                                              "has_f64", "precision")] + [
+        ("scene_lds_bytes", ctypes.c_int64), ("scene_lds_bytes_oct", ctypes.c_int64)]
+
+
+class PlanAnswer(ctypes.Structure):
+    """frt_plan_answer: the dispatch's return code, the plan's fields and the kernel handles' offsets."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rc", "stack", "waves", "lds_scene", "wide", "f64")] + [
+        (n, ctypes.c_int64) for n in ("lds", "scene_lds", "lds_boot")] + [
+        ("kernel", ctypes.c_uint64), ("kernel_boot", ctypes.c_uint64)]
+
+
 class HostSceneInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n_tris", "n_spheres", "n_materials", "n_lights", "n_nodes",
                                               "world_kind", "n_list", "bvh_depth")] + [
@@ -204,7 +219,8 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_set_env_image", "frt_scene_set_env_image", "frt_scene_env_image", "frt_read_hdr",
            "frt_selftest_path_host_env")
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
-EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance")
+EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
+             "frtx_selftest_plan")
 
 
 def lib():
@@ -722,6 +738,39 @@ def selftest_trace_host(scene, rays):
     _check(lib().frtx_selftest_trace_host(ctypes.byref(view), rays.ctypes.data, len(rays), hits.ctypes.data),
            "frtx_selftest_trace_host")
     return hits
+
+
+_handles = None
+
+
+def kernel_handles():
+    """{symbol value: name} of the library's kernel handles, from its symbol table (`nm`): a
+    kernel's host-side handle carries the kernel's mangled name, beside its launch stub
+    `__device_stub__<name>`."""
+    global _handles
+    if _handles is None:
+        import re
+        import subprocess
+        out = subprocess.run(["nm", "--defined-only", LIB_PATH], capture_output=True, text=True, check=True).stdout
+        syms = [l.split() for l in out.splitlines()]
+        stub = re.compile(r"(\d+)__device_stub__")
+        kernels = {stub.sub(lambda m: str(int(m.group(1)) - 15), f[2]) for f in syms if len(f) == 3 and stub.search(f[2])}
+        _handles = {int(f[0], 16): f[2] for f in syms if len(f) == 3 and f[2] in kernels}
+    return _handles
+
+
+def selftest_plan(**query):
+    """The launch plan of a call without a device (frtx_selftest_plan): query = PlanQuery
+    fields.  Returns the PlanAnswer fields as a dict, the kernels by name (None: no kernel, or a
+    handle the symbol table does not name)."""
+    f = lib().frtx_selftest_plan
+    f.argtypes = [ctypes.POINTER(PlanQuery), ctypes.POINTER(PlanAnswer)]
+    a = PlanAnswer()
+    _check(f(ctypes.byref(PlanQuery(**query)), ctypes.byref(a)), "frtx_selftest_plan")
+    d = {n: getattr(a, n) for n, _ in a._fields_}
+    for k in ("kernel", "kernel_boot"):
+        d[k] = kernel_handles().get(d[k]) if d[k] else None
+    return d
 
 
 def selftest_mlt_paths_host(scene, nx, ny, seed, n):

@@ -2,8 +2,26 @@
 // renders a context's scene, and with how much LDS.  Included only by the units
 // that instantiate kernels: a plan template emits the kernels it names into
 // the unit that calls it.
+//
+// The plans come in two shapes, and the kernel set is exactly what the two emit:
+//  * the fixed shape (walk_plan): one rung per residency and stack class -- the
+//    list world (stack 16); the octant copies or the planar tree in LDS (8 / 16);
+//    the 4-wide tree (kBvh4LdsStack); the binary tree from HBM (16 / 32, then 64
+//    without a register cap); deeper: FRT_E_UNSUPPORTED.  Every integrator but
+//    the default path render walks it, as do the path kernels of the estimator
+//    flags, PSS-MLT and the ray queries: plan_fixed (path_megakernel with one
+//    register cap per residency), pick_mlt and pick_trace (frt_render.hip) hand
+//    it a callable that names the kernel of a rung.  A flag's kernels cover every
+//    rung, so a flag never falls back to a kernel without it.
+//  * the tunable shape (pick_launcher_t): the default path render, the one the
+//    benchmarks time.  It has two rungs the fixed shape lacks, a stack-8 kernel
+//    from HBM and a stack-24 one, and its register cap is a run-time choice
+//    (bvh_launcher: the A/B flags FRT_FLAG_WAVES*, FRT_MATS_WAVES) with one
+//    kernel per cap.  Folding it into the walk would add or drop kernels.
+// fp64 renders have a rule of their own, plan_f64.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "frt_ctx.hpp"
 
@@ -90,10 +108,11 @@ constexpr bool kSplitLds = false;
 constexpr bool kSplitLds = true;
 #endif
 namespace frt_lds {
-int path_oct(int stack, int waves, size_t scene_bytes, Launcher &L);
-int path_oct_roulette(int stack, size_t scene_bytes, Launcher &L);   // FRT_FLAG_ROULETTE: the 5-wave kernels
-int path_oct_sobol(int stack, bool roulette, size_t scene_bytes, Launcher &L);   // FRT_FLAG_SOBOL [| _ROULETTE]: the same
-int mlt_oct(int stack, const void **boot, const void **chains);
+// each answers FRT_E_UNSUPPORTED unless the context's rung is an octant one
+int path_oct(const frt_ctx *c, int flags, int waves, Launcher &L);   // the tunable shape's rung
+// FRT_FLAG_ROULETTE, FRT_FLAG_SOBOL: the 5-wave kernels of the sets features = kMatsRoulette, kMatsSobol or both
+int path_oct_features(const frt_ctx *c, int flags, int features, Launcher &L);
+int mlt_oct(const frt_ctx *c, int flags, const void **boot, const void **chains);
 }  // namespace frt_lds
 
 // MATS: the material set the kernel is compiled for (kMats* mask, frt_path.hpp)
@@ -139,7 +158,7 @@ static int pick_launcher_t(const frt_ctx *c, int flags, Launcher &L)
     // LDS-resident binary tree: the per-octant node copies when they fit
     if (oct) {
         if constexpr (MATS == kMatsNone && kSplitLds) {   // the third unit's kernels (frt_lds)
-            return frt_lds::path_oct(d < 8 ? 8 : 16, waves, c->scene_lds_bytes_oct, L);
+            return frt_lds::path_oct(c, flags, waves, L);
         } else {
             L = d < 8 ? bvh_launcher<8, true, kWorldBvh2Oct, MATS>(waves, c->scene_lds_bytes_oct)
                       : bvh_launcher<16, true, kWorldBvh2Oct, MATS>(waves, c->scene_lds_bytes_oct);
@@ -156,112 +175,98 @@ static int pick_launcher_t(const frt_ctx *c, int flags, Launcher &L)
     else return FRT_E_UNSUPPORTED;
     return FRT_OK;
 }
-// AO / normals: the default plans only (LDS-resident binary BVH, HBM 4-wide or
-// binary), register caps as for path; ao keeps the specular generate() code
-// (M = kMatsAll), normals has none (kMatsNone); a context with an environment
-// image runs both with kMatsEnv (the lookup on a miss).
-template <int KIND, int M>
-static int pick_launcher_kind(const frt_ctx *c, int flags, Launcher &L)
-{
-    if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, M, KIND>(0); return FRT_OK; }
-    const int d = c->stack_needed;
-    const size_t sb = c->scene_lds_bytes;
-    const auto [lds, oct, wide] = residency(c, flags);
-    if (oct) {
-        L = d < 8 ? make_launcher<8, kWorldBvh2Oct, true, 5, M, KIND>(c->scene_lds_bytes_oct)
-                  : make_launcher<16, kWorldBvh2Oct, true, 5, M, KIND>(c->scene_lds_bytes_oct);
-    } else if (lds) {
-        L = d < 8 ? make_launcher<8, FRT_WORLD_BVH, true, 5, M, KIND>(sb)
-                  : make_launcher<16, FRT_WORLD_BVH, true, 5, M, KIND>(sb);
-    } else if (wide) {
-        L = make_launcher<kBvh4LdsStack, kWorldBvh4, false, 6, M, KIND>(0);
-    } else if (d < 16) {
-        L = make_launcher<16, FRT_WORLD_BVH, false, 6, M, KIND>(0);
-    } else if (d < 32) {
-        L = make_launcher<32, FRT_WORLD_BVH, false, 6, M, KIND>(0);
-    } else if (d < 64) {
-        L = make_launcher<64, FRT_WORLD_BVH, false, 1, M, KIND>(0);
-    } else {
-        return FRT_E_UNSUPPORTED;
+
+// ---- the fixed shape ----
+// A rung as compile-time constants, and the register cap a plan gives it out of
+// its three: the scene in LDS, the binary tree from HBM, the 4-wide tree.  The
+// list world and the 64-entry stack take the compiler's own allocation.
+template <int STACK, int WORLD, bool LDS>
+struct Rung {
+    static constexpr int stack = STACK, world = WORLD;
+    static constexpr bool lds = LDS;
+    template <int W_LDS, int W_HBM, int W_WIDE>
+    static constexpr int cap()
+    {
+        return LDS ? W_LDS : WORLD == kWorldBvh4 ? W_WIDE : (WORLD == FRT_WORLD_LIST || STACK == 64) ? 1 : W_HBM;
     }
-    return FRT_OK;
+};
+// f(rung, scene bytes the rung loads into LDS) for the rung of the context's scene; its return code
+template <typename F>
+static int walk_plan(const frt_ctx *c, int flags, F &&f)
+{
+    if (c->world_kind == FRT_WORLD_LIST) return f(Rung<16, FRT_WORLD_LIST, false>{}, size_t(0));
+    const int d = c->stack_needed;
+    const auto [lds, oct, wide] = residency(c, flags);
+    if (oct) return d < 8 ? f(Rung<8, kWorldBvh2Oct, true>{}, c->scene_lds_bytes_oct)
+                          : f(Rung<16, kWorldBvh2Oct, true>{}, c->scene_lds_bytes_oct);
+    if (lds) return d < 8 ? f(Rung<8, FRT_WORLD_BVH, true>{}, c->scene_lds_bytes)
+                          : f(Rung<16, FRT_WORLD_BVH, true>{}, c->scene_lds_bytes);
+    if (wide) return f(Rung<kBvh4LdsStack, kWorldBvh4, false>{}, size_t(0));
+    if (d < 16) return f(Rung<16, FRT_WORLD_BVH, false>{}, size_t(0));
+    if (d < 32) return f(Rung<32, FRT_WORLD_BVH, false>{}, size_t(0));
+    if (d < 64) return f(Rung<64, FRT_WORLD_BVH, false>{}, size_t(0));
+    return FRT_E_UNSUPPORTED;
 }
-// fp64 kernels (path only; DESIGN.md "Precision"): the list world with the
-// scene's material set, or the binary tree from HBM with every material
-// compiled in (the debugging build; no register cap, stack 32 or 64)
+// The fixed shape with path_megakernel<MATS, KIND>: one register cap per residency, so the
+// FRT_FLAG_WAVES* A/B flags and FRT_MATS_WAVES do not apply.  Its users:
+//  * AO, normals, albedo, depth: caps 5, 6, 6.  AO keeps the specular generate() code (kMatsAll),
+//    normals has none (kMatsNone); a context with an environment image runs both with kMatsEnv;
+//  * the path kernels of FRT_FLAG_ENV_SAMPLING (kMatsEnvNee), FRT_FLAG_ROULETTE (kMatsRoulette)
+//    and FRT_FLAG_SOBOL (kMatsSobol): the caps of the sibling kernels without the flag -- 4, 5, 5
+//    with every material (the material unit), 5, 6, 7 (FRT_EXP_W6, FRT_EXP_W7) for a lambertian
+//    scene without an image (the main unit).  The latter's octant rung comes from frt_lds, under
+//    that unit's scheduler flag.
+template <int MATS, int KIND, int W_LDS, int W_HBM, int W_WIDE>
+static int plan_fixed(const frt_ctx *c, int flags, Launcher &L)
+{
+    return walk_plan(c, flags, [&](auto r, size_t scene_bytes) -> int {
+        using R = decltype(r);
+        if constexpr (R::world == kWorldBvh2Oct && kSplitLds && KIND == FRT_INTEGRATOR_PATH &&
+                      (MATS & kMatsFeatures) != 0 && (MATS & ~kMatsFeatures) == 0) {
+            static_assert(W_LDS == 5, "frt_lds::path_oct_features holds the 5-wave kernels");
+            return frt_lds::path_oct_features(c, flags, MATS, L);
+        } else {
+            L = make_launcher<R::stack, R::world, R::lds, R::template cap<W_LDS, W_HBM, W_WIDE>(), MATS, KIND>(scene_bytes);
+            return FRT_OK;
+        }
+    });
+}
+// f(std::integral_constant<int, features>) for a non-empty set of kMatsFeatures bits
+template <typename F>
+static int with_features(int features, F &&f)
+{
+    switch (features) {
+    case kMatsRoulette: return f(std::integral_constant<int, kMatsRoulette>{});
+    case kMatsSobol: return f(std::integral_constant<int, kMatsSobol>{});
+    case kMatsSobol | kMatsRoulette: return f(std::integral_constant<int, kMatsSobol | kMatsRoulette>{});
+    default: return FRT_E_INVALID;
+    }
+}
+
+// fp64 kernels (path only; DESIGN.md "Precision"): the list world, or the binary tree from HBM
+// (stack 32 or 64), no register cap.  BVH = false: the list rung alone -- the main unit's
+// lambertian sets and the material unit's smaller sets have no kernel for a tree (a BVH world's
+// fp64 render of those scenes takes the every-material kernels, the debugging build).
 #ifndef FRT_EXP_F64_LIST_WAVES
 #define FRT_EXP_F64_LIST_WAVES 1   // experiment builds: register cap of the fp64 list kernels (1 = the compiler's own)
 #endif
-template <int MATS>
-static int pick_launcher_f64_t(const frt_ctx *c, Launcher &L)
+template <int MATS, bool BVH = true>
+static int plan_f64(const frt_ctx *c, Launcher &L)
 {
+    // (a 2-wave register cap changed nothing: profiles/r03/r03c_ab_veach_listbox_f64waves.jsonl; the
+    // knob covers the sets with a material or a feature bit, the plain lambertian kernel has none)
+    constexpr int kListCap = MATS == kMatsNone ? 1 : FRT_EXP_F64_LIST_WAVES;
     if (c->world_kind == FRT_WORLD_LIST) {
-        // (a 2-wave register cap changed nothing: profiles/r03/r03c_ab_veach_listbox_f64waves.jsonl)
-        L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, MATS, FRT_INTEGRATOR_PATH, double>(0);
+        L = make_launcher<16, FRT_WORLD_LIST, false, kListCap, MATS, FRT_INTEGRATOR_PATH, double>(0);
         return FRT_OK;
     }
-    const int d = c->stack_needed;
-    constexpr int kAll = kMatsAll | (MATS & kMatsEnv);
-    if (d < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, kAll, FRT_INTEGRATOR_PATH, double>(0);
-    else if (d < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, kAll, FRT_INTEGRATOR_PATH, double>(0);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
-}
-// Path renders with FRT_FLAG_ROULETTE (the kMatsRoulette kernels): as the
-// kernels of FRT_FLAG_ENV_SAMPLING, one register cap per residency -- W_LDS,
-// W_HBM, W_WIDE, the defaults of the sibling kernels without roulette -- so the
-// FRT_FLAG_WAVES* A/B flags and FRT_MATS_WAVES do not apply.  Every residency a
-// context can have is covered: the flag never falls back to a kernel without
-// roulette.  The octant plan's lambertian kernels come from frt_lds
-// (path_oct_roulette), under that unit's scheduler flag.
-// The kMatsSobol kernels (FRT_FLAG_SOBOL, with or without roulette) take the
-// same plans with the same caps: MATS then carries kMatsSobol, and the octant
-// plan's lambertian kernels are frt_lds::path_oct_sobol's.
-template <int MATS, int W_LDS, int W_HBM, int W_WIDE>
-static int pick_launcher_roulette_t(const frt_ctx *c, int flags, Launcher &L)
-{
-    static_assert((MATS & kMatsFeatures) != 0, "the roulette and Sobol' kernels' plans");
-    if (c->world_kind == FRT_WORLD_LIST) { L = make_launcher<16, FRT_WORLD_LIST, false, 1, MATS>(0); return FRT_OK; }
-    const int d = c->stack_needed;
-    const size_t sb = c->scene_lds_bytes;
-    const auto [lds, oct, wide] = residency(c, flags);
-    if (oct) {
-        if constexpr (MATS == kMatsRoulette && kSplitLds) {
-            return frt_lds::path_oct_roulette(d < 8 ? 8 : 16, c->scene_lds_bytes_oct, L);
-        } else if constexpr ((MATS & ~kMatsRoulette) == kMatsSobol && kSplitLds) {
-            return frt_lds::path_oct_sobol(d < 8 ? 8 : 16, (MATS & kMatsRoulette) != 0, c->scene_lds_bytes_oct, L);
-        } else {
-            L = d < 8 ? make_launcher<8, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct)
-                      : make_launcher<16, kWorldBvh2Oct, true, W_LDS, MATS>(c->scene_lds_bytes_oct);
-        }
-    } else if (lds) {
-        L = d < 8 ? make_launcher<8, FRT_WORLD_BVH, true, W_LDS, MATS>(sb)
-                  : make_launcher<16, FRT_WORLD_BVH, true, W_LDS, MATS>(sb);
-    } else if (wide) {
-        L = make_launcher<kBvh4LdsStack, kWorldBvh4, false, W_WIDE, MATS>(0);
-    } else if (d < 16) {
-        L = make_launcher<16, FRT_WORLD_BVH, false, W_HBM, MATS>(0);
-    } else if (d < 32) {
-        L = make_launcher<32, FRT_WORLD_BVH, false, W_HBM, MATS>(0);
-    } else if (d < 64) {
-        L = make_launcher<64, FRT_WORLD_BVH, false, 1, MATS>(0);
-    } else {
-        return FRT_E_UNSUPPORTED;
+    if constexpr (BVH) {
+        if (c->stack_needed < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
+        else if (c->stack_needed < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
+        else return FRT_E_UNSUPPORTED;
+        return FRT_OK;
     }
-    return FRT_OK;
-}
-// ... and their fp64 kernels: the list world, or the binary tree from HBM
-// (stack 32 or 64), no register cap
-template <int MATS>
-static int pick_launcher_roulette_f64_t(const frt_ctx *c, Launcher &L)
-{
-    static_assert((MATS & kMatsFeatures) != 0, "the roulette and Sobol' kernels' plans");
-    if (c->world_kind == FRT_WORLD_LIST)
-        L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, MATS, FRT_INTEGRATOR_PATH, double>(0);
-    else if (c->stack_needed < 32) L = make_launcher<32, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
-    else if (c->stack_needed < 64) L = make_launcher<64, FRT_WORLD_BVH, false, 1, MATS, FRT_INTEGRATOR_PATH, double>(0);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
+    return FRT_E_UNSUPPORTED;
 }
 template <int STACK, int WORLD, bool LDS, bool MATS, bool ENV = false>
 static void mlt_kernels_t(const void **boot, const void **chains)
@@ -272,27 +277,19 @@ static void mlt_kernels_t(const void **boot, const void **chains)
 
 // the material unit's entry points (frt_render_mats.hip)
 namespace frt_mats {
-// path (KIND = FRT_INTEGRATOR_PATH, fp32), fp64 path (f64) or AO: the plan for
-// the scene's material set c->mats (!= kMatsNone); and every integrator of a
-// context with an environment image (the kMatsEnv kernels)
-int pick(const frt_ctx *c, int integrator, int flags, bool f64, Launcher &L);
-// the path kernels that also sample the environment image (FRT_FLAG_ENV_SAMPLING)
-int pick_env_sampling(const frt_ctx *c, int flags, bool f64, Launcher &L);
-// the path kernels with Russian roulette (FRT_FLAG_ROULETTE) of every scene but
-// the lambertian ones without an image (those: the main unit and frt_lds);
-// env_sampling: the kernels that also sample the image
-int pick_roulette(const frt_ctx *c, int flags, bool f64, bool env_sampling, Launcher &L);
-// the path kernels of FRT_FLAG_SOBOL (roulette: with FRT_FLAG_ROULETTE as well) of the
-// same scenes, on the same plans and caps
-int pick_sobol(const frt_ctx *c, int flags, bool f64, bool env_sampling, bool roulette, Launcher &L);
-// PSS-MLT with the material branch or (env) the environment image, for the
-// (stack, world, lds) plans of render_mlt
-int mlt(int stack, int world, bool lds, bool env, const void **boot, const void **chains);
+// Every kernel with a material set: path (fp32 or f64) and AO of a scene with materials
+// (c->mats != kMatsNone), every integrator of a context with an environment image (kMatsEnv),
+// the path kernels that sample it (env_sampling: kMatsEnvNee), and the path kernels of
+// FRT_FLAG_ROULETTE / _SOBOL (features: their kMatsFeatures bits, 0 = none) of every scene but
+// the lambertian ones without an image (those: the main unit and frt_lds).
+int pick(const frt_ctx *c, int integrator, int flags, bool f64, bool env_sampling, int features, Launcher &L);
+// PSS-MLT with the material branch or (env) the environment image
+int mlt(const frt_ctx *c, int flags, bool env, const void **boot, const void **chains);
 }  // namespace frt_mats
 
 // the feature unit's entry point (frt_render_feat.hip): the kernels of
 // FRT_INTEGRATOR_ALBEDO and FRT_INTEGRATOR_DEPTH, on the plans of normals
-// (pick_launcher_kind).  One kernel set for every scene and context: albedo
+// (plan_fixed).  One kernel set for every scene and context: albedo
 // always carries the texture lookup, and neither reads the environment, so a
 // context with an image runs them too (no kMatsEnv variant).
 namespace frt_feat {

@@ -2,6 +2,7 @@
 // normals, ray-query and PSS-MLT kernels (frt_kernels.hpp, frt_plans.hpp), the
 // film reductions, and the C-ABI of include/frt.h that launches them.
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 
 #include <algorithm>
 #include <cfloat>
@@ -400,43 +401,29 @@ static bool use_f64(const frt_ctx *c, const frt_render_params *p)
     if (p->flags & FRT_FLAG_FP64) return true;
     return c->precision == FRT_PRECISION_FP64 || (c->precision == FRT_PRECISION_AUTO && c->world_kind == FRT_WORLD_LIST);
 }
+// The plan of a render: integrator and flags -> material set and unit -> ladder (frt_plans.hpp)
 static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &L, bool f64, bool env_sampling)
 {
     if (f64 && !c->has_f64) return FRT_E_INVALID;
     if (integrator == FRT_INTEGRATOR_ALBEDO || integrator == FRT_INTEGRATOR_DEPTH)   // no estimator flag, no image
         return frt_feat::pick(c, integrator, flags, L);
-    if ((flags & FRT_FLAG_SOBOL) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsSobol kernels, the roulette kernels' plans
-        const bool rl = (flags & FRT_FLAG_ROULETTE) != 0;
-        if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
-            return frt_mats::pick_sobol(c, flags, f64, env_sampling, rl, L);
-        if (f64) {   // a lambertian list world
-            if (rl) L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsSobol | kMatsRoulette, FRT_INTEGRATOR_PATH, double>(0);
-            else L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsSobol, FRT_INTEGRATOR_PATH, double>(0);
-            return FRT_OK;
-        }
-        return rl ? pick_launcher_roulette_t<kMatsSobol | kMatsRoulette, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L)
-                  : pick_launcher_roulette_t<kMatsSobol, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L);
-    }
-    if ((flags & FRT_FLAG_ROULETTE) && integrator == FRT_INTEGRATOR_PATH) {   // the kMatsRoulette kernels
-        if (env_sampling || c->env_texels || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
-            return frt_mats::pick_roulette(c, flags, f64, env_sampling, L);
-        // a lambertian scene without an image: the sibling plans' caps (5 waves from LDS, 6 from HBM, 7 on the 4-wide tree)
-        if (f64) {   // a lambertian list world, as below
-            L = make_launcher<16, FRT_WORLD_LIST, false, FRT_EXP_F64_LIST_WAVES, kMatsRoulette, FRT_INTEGRATOR_PATH, double>(0);
-            return FRT_OK;
-        }
-        return pick_launcher_roulette_t<kMatsRoulette, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L);
-    }
-    if (env_sampling) return frt_mats::pick_env_sampling(c, flags, f64, L);   // the kMatsEnvNee kernels
-    if (c->env_texels) return frt_mats::pick(c, integrator, flags, f64, L);   // the kMatsEnv kernels
-    if (integrator == FRT_INTEGRATOR_NORMALS) return pick_launcher_kind<FRT_INTEGRATOR_NORMALS, kMatsNone>(c, flags, L);
-    if (integrator == FRT_INTEGRATOR_AO || c->mats != kMatsNone || (f64 && c->world_kind != FRT_WORLD_LIST))
-        return frt_mats::pick(c, integrator, flags, f64, L);   // every kernel with a material set
-    if (f64) {   // a lambertian list world (BVH worlds' fp64 kernels carry every material: the other unit)
-        L = make_launcher<16, FRT_WORLD_LIST, false, 1, kMatsNone, FRT_INTEGRATOR_PATH, double>(0);
-        return FRT_OK;
-    }
-    return pick_launcher_t<kMatsNone>(c, flags, L);
+    // FRT_FLAG_ROULETTE, FRT_FLAG_SOBOL (path): the kernels compiled with these kMatsFeatures bits
+    const int features = integrator != FRT_INTEGRATOR_PATH ? 0 : ((flags & FRT_FLAG_ROULETTE) ? kMatsRoulette : 0) |
+                                                                     ((flags & FRT_FLAG_SOBOL) ? kMatsSobol : 0);
+    // the material unit holds every kernel with a material set: an image's lookup, AO, the scene's
+    // materials, and the fp64 kernels of BVH worlds (they carry every material)
+    if (env_sampling || c->env_texels ||
+        (integrator != FRT_INTEGRATOR_NORMALS && (integrator == FRT_INTEGRATOR_AO || c->mats != kMatsNone ||
+                                                  (f64 && c->world_kind != FRT_WORLD_LIST))))
+        return frt_mats::pick(c, integrator, flags, f64, env_sampling, features, L);
+    // a lambertian scene without an image (fp64: a list world)
+    if (integrator == FRT_INTEGRATOR_NORMALS) return plan_fixed<kMatsNone, FRT_INTEGRATOR_NORMALS, 5, 6, 6>(c, flags, L);
+    if (features)   // the sibling plans' caps: 5 waves from LDS, 6 from HBM, 7 on the 4-wide tree
+        return with_features(features, [&](auto x) -> int {
+            constexpr int M = decltype(x)::value;
+            return f64 ? plan_f64<M, false>(c, L) : plan_fixed<M, FRT_INTEGRATOR_PATH, 5, FRT_EXP_W6, FRT_EXP_W7>(c, flags, L);
+        });
+    return f64 ? plan_f64<kMatsNone, false>(c, L) : pick_launcher_t<kMatsNone>(c, flags, L);
 }
 
 
@@ -471,27 +458,12 @@ static TraceLauncher trace_waves(size_t sb)
 }
 static int pick_trace(const frt_ctx *c, int flags, TraceLauncher &L)
 {
-    if (c->world_kind == FRT_WORLD_LIST) { L = make_trace<16, FRT_WORLD_LIST, false, 8>(0); return FRT_OK; }
-    const int d = c->stack_needed;
-    const auto [lds, oct, wide] = residency(c, flags);
-    if (oct) {
-        L = d < 8 ? trace_waves<8, kWorldBvh2Oct, true>(c->scene_lds_bytes_oct)
-                  : trace_waves<16, kWorldBvh2Oct, true>(c->scene_lds_bytes_oct);
-    } else if (lds) {
-        L = d < 8 ? make_trace<8, FRT_WORLD_BVH, true, 8>(c->scene_lds_bytes)
-                  : make_trace<16, FRT_WORLD_BVH, true, 8>(c->scene_lds_bytes);
-    } else if (wide) {
-        L = trace_waves<kBvh4LdsStack, kWorldBvh4, false>(0);
-    } else if (d < 16) {
-        L = make_trace<16, FRT_WORLD_BVH, false, 8>(0);
-    } else if (d < 32) {
-        L = make_trace<32, FRT_WORLD_BVH, false, 8>(0);
-    } else if (d < 64) {
-        L = make_trace<64, FRT_WORLD_BVH, false, 1>(0);
-    } else {
-        return FRT_E_UNSUPPORTED;
-    }
-    return FRT_OK;
+    return walk_plan(c, flags, [&](auto r, size_t scene_bytes) -> int {
+        using R = decltype(r);
+        if constexpr (R::world == kWorldBvh2Oct || R::world == kWorldBvh4) L = trace_waves<R::stack, R::world, R::lds>(scene_bytes);
+        else L = make_trace<R::stack, R::world, R::lds, R::stack == 64 ? 1 : 8>(scene_bytes);
+        return FRT_OK;
+    });
 }
 
 // Batched Scene::world->hit (include/frt.h frt_trace_device)
@@ -546,19 +518,6 @@ extern "C" int frt_trace_device(frt_ctx *c, const float *rays, int64_t n, float 
 }
 
 // ---- PSS-MLT render: bootstrap b, then the chain megakernel splatting into dev_film ----
-// PSS-MLT kernels of a plan: the material branch from the material unit
-template <int STACK, int WORLD, bool LDS = false>
-static int mlt_kernels(bool mats, bool env, const void **boot, const void **chains)
-{
-    if (mats || env) return frt_mats::mlt(STACK, WORLD, LDS, env, boot, chains);
-    if constexpr (WORLD == kWorldBvh2Oct && kSplitLds) {
-        static_assert(STACK == 8 || STACK == 16, "frt_lds::mlt_oct holds the 8- and 16-entry kernels");
-        return frt_lds::mlt_oct(STACK, boot, chains);
-    } else {
-        mlt_kernels_t<STACK, WORLD, LDS, false>(boot, chains);
-        return FRT_OK;
-    }
-}
 
 #if defined(FRT_DIAG)
 // diagnostic builds only: the per-phase counters of the last path or PSS-MLT
@@ -594,32 +553,51 @@ extern "C" int frt_diag_read(unsigned long long *out)
 }
 #endif
 
+// The PSS-MLT plan of a context: the bootstrap and chain kernels, the traversal stack and the
+// LDS bytes of the two launches.  No device call: frtx_selftest_plan asks it too.
+struct MltPlan {
+    const void *boot = nullptr, *chain = nullptr;
+    int stack = 0;
+    size_t lds_boot = 0, lds = 0;
+    bool lds_scene = false, oct = false;
+};
+static int pick_mlt(frt_ctx *c, int flags, MltPlan &P)
+{
+    const bool env = c->env_texels != nullptr;   // the chain kernels with the environment lookup
+    bool rung = false;
+    size_t scene_lds = 0;
+    // the octant node copies when they fit, as the path kernels (round 5: the chain kernel used the planar tree)
+    const int krc = walk_plan(c, flags, [&](auto r, size_t scene_bytes) -> int {
+        using R = decltype(r);
+        rung = true;
+        P.stack = R::world == FRT_WORLD_LIST ? 0 : R::stack;
+        P.lds_scene = R::lds; P.oct = R::world == kWorldBvh2Oct;
+        scene_lds = scene_bytes;
+        // the material branch and the image's lookup from the material unit, the lambertian octant kernels from frt_lds
+        if (c->has_spec_mats || env) return frt_mats::mlt(c, flags, env, &P.boot, &P.chain);
+        if constexpr (R::world == kWorldBvh2Oct && kSplitLds) {
+            return frt_lds::mlt_oct(c, flags, &P.boot, &P.chain);
+        } else {
+            mlt_kernels_t<R::stack, R::world, R::lds, false>(&P.boot, &P.chain);
+            return FRT_OK;
+        }
+    });
+    if (!rung) return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
+    if (krc != FRT_OK || !P.boot || !P.chain) return set_err(c, FRT_E_UNSUPPORTED, "pssmlt: no kernels for this plan in this build");
+    P.lds_boot = (size_t)P.stack * kBlock * sizeof(int);
+    P.lds = P.lds_boot + (size_t)kChainWords * kBlock * sizeof(int) + scene_lds;
+    return FRT_OK;
+}
+
 static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, hipStream_t st, frt_stats *stats)
 {
     const auto t_start = std::chrono::steady_clock::now();
-    int stack, krc;
-    const void *kboot = nullptr, *kchain = nullptr;
-    const int d = c->stack_needed;
-    // the octant node copies when they fit, as the path kernels (round 5: the chain kernel used the planar tree)
-    const auto [lds_scene, oct, wide] = residency(c, p->flags);
-    const bool env = c->env_texels != nullptr;   // the chain kernels with the environment lookup
-    if (c->world_kind == FRT_WORLD_LIST) { stack = 0; krc = mlt_kernels<16, FRT_WORLD_LIST>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (wide) {
-        stack = kBvh4LdsStack;
-        krc = mlt_kernels<kBvh4LdsStack, kWorldBvh4>(c->has_spec_mats, env, &kboot, &kchain);
-    }
-    else if (oct && d < 8) { stack = 8; krc = mlt_kernels<8, kWorldBvh2Oct, true>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (oct) { stack = 16; krc = mlt_kernels<16, kWorldBvh2Oct, true>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (lds_scene && d < 8) { stack = 8; krc = mlt_kernels<8, FRT_WORLD_BVH, true>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (lds_scene) { stack = 16; krc = mlt_kernels<16, FRT_WORLD_BVH, true>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (d < 16) { stack = 16; krc = mlt_kernels<16, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (d < 32) { stack = 32; krc = mlt_kernels<32, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
-    else if (d < 64) { stack = 64; krc = mlt_kernels<64, FRT_WORLD_BVH>(c->has_spec_mats, env, &kboot, &kchain); }
-    else return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
-    if (krc != FRT_OK || !kboot || !kchain) return set_err(c, FRT_E_UNSUPPORTED, "pssmlt: no kernels for this plan in this build");
-    const size_t lds_boot = (size_t)stack * kBlock * sizeof(int);
-    const size_t lds = lds_boot + (size_t)kChainWords * kBlock * sizeof(int) +
-                       (oct ? c->scene_lds_bytes_oct : lds_scene ? c->scene_lds_bytes : 0);
+    MltPlan P;
+    if (const int prc = pick_mlt(c, p->flags, P)) return prc;
+    const void *const kboot = P.boot, *const kchain = P.chain;
+    const int stack = P.stack;
+    const size_t lds_boot = P.lds_boot, lds = P.lds;
+    const bool lds_scene = P.lds_scene, oct = P.oct;
     const uint32_t n_chains = (uint32_t)p->mlt_chains;
     const uint32_t n_local = (n_chains > (uint32_t)p->shard_index)
                                  ? (n_chains - 1 - (uint32_t)p->shard_index) / (uint32_t)p->shard_count + 1 : 0;
@@ -1097,6 +1075,48 @@ extern "C" int frt_render(frt_ctx *c, const frt_render_params *p, float *film_rg
         film_rgb[3 * (size_t)px + 0] = host[3 * s + 0];
         film_rgb[3 * (size_t)px + 1] = host[3 * s + 1];
         film_rgb[3 * (size_t)px + 2] = host[3 * s + 2];
+    }
+    return FRT_OK;
+}
+
+// The launch plan of a call on a context with the queried scene properties (include/frt.h): the
+// dispatch above over a context built here, which needs no device.  A kernel is answered as the
+// offset of its host-side handle in the library; the handle's symbol carries the kernel's name.
+extern "C" int frtx_selftest_plan(const frt_plan_query *q, frt_plan_answer *a)
+{
+    if (!q || !a) return FRT_E_INVALID;
+    memset(a, 0, sizeof(*a));
+    static float4 texel;   // an image: the dispatch reads only that the pointer is set
+    frt_ctx c;
+    c.world_kind = q->world_kind; c.stack_needed = q->stack_needed;
+    c.scene_lds_bytes = (size_t)q->scene_lds_bytes; c.scene_lds_bytes_oct = (size_t)q->scene_lds_bytes_oct;
+    c.has_bvh4 = q->has_bvh4 != 0; c.depth4 = q->depth4;
+    c.mats = q->mats; c.has_spec_mats = q->has_spec_mats != 0;
+    c.env_texels = q->env_image ? &texel : nullptr;
+    c.has_f64 = q->has_f64 != 0; c.precision = q->precision;
+    auto handle = [](const void *fn) -> uint64_t {
+        Dl_info info;
+        return fn && dladdr(fn, &info) ? (uint64_t)((const char *)fn - (const char *)info.dli_fbase) : 0;
+    };
+    if (q->kind == 1) {
+        TraceLauncher L;
+        a->rc = pick_trace(&c, q->flags, L);
+        a->lds = (int64_t)L.lds; a->waves = L.waves; a->lds_scene = L.lds_scene; a->scene_lds = (int64_t)L.scene_lds;
+        a->kernel = handle(L.fn);
+    } else if (q->integrator == FRT_INTEGRATOR_PSSMLT) {
+        MltPlan P;
+        a->rc = pick_mlt(&c, q->flags, P);
+        a->stack = P.stack; a->lds = (int64_t)P.lds; a->lds_boot = (int64_t)P.lds_boot; a->lds_scene = P.lds_scene;
+        a->scene_lds = (int64_t)(P.oct ? c.scene_lds_bytes_oct : P.lds_scene ? c.scene_lds_bytes : 0);
+        a->kernel = handle(P.chain); a->kernel_boot = handle(P.boot);
+    } else {
+        frt_render_params p{};
+        p.integrator = q->integrator; p.flags = q->flags;
+        Launcher L;
+        a->rc = pick_launcher(&c, q->integrator, q->flags, L, use_f64(&c, &p), q->env_sampling != 0);
+        a->lds = (int64_t)L.lds; a->stack = L.stack; a->waves = L.waves; a->lds_scene = L.lds_scene; a->wide = L.wide;
+        a->f64 = L.f64; a->scene_lds = (int64_t)L.scene_lds;
+        a->kernel = handle(L.fn);
     }
     return FRT_OK;
 }

@@ -11,14 +11,19 @@
 #include "frt_kernels.hpp"
 #include "frt_plans.hpp"
 
-int frt_lds::mlt_oct(int stack, const void **boot, const void **chains)
+int frt_lds::mlt_oct(const frt_ctx *c, int flags, const void **boot, const void **chains)
 {
 #if defined(FRT_OCT_IN_MAIN)
     return FRT_E_UNSUPPORTED;
 #else
-    if (stack == 8) mlt_kernels_t<8, kWorldBvh2Oct, true, false>(boot, chains);
-    else if (stack == 16) mlt_kernels_t<16, kWorldBvh2Oct, true, false>(boot, chains);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
+    return walk_plan(c, flags, [&](auto r, size_t) -> int {
+        using R = decltype(r);
+        if constexpr (R::world == kWorldBvh2Oct) {
+            mlt_kernels_t<R::stack, kWorldBvh2Oct, true, false>(boot, chains);
+            return FRT_OK;
+        } else {
+            return FRT_E_UNSUPPORTED;
+        }
+    });
 #endif
 }

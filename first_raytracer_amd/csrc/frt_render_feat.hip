@@ -8,7 +8,7 @@
 
 int frt_feat::pick(const frt_ctx *c, int integrator, int flags, Launcher &L)
 {
-    if (integrator == FRT_INTEGRATOR_ALBEDO) return pick_launcher_kind<FRT_INTEGRATOR_ALBEDO, kMatsNone>(c, flags, L);
-    if (integrator == FRT_INTEGRATOR_DEPTH) return pick_launcher_kind<FRT_INTEGRATOR_DEPTH, kMatsNone>(c, flags, L);
+    if (integrator == FRT_INTEGRATOR_ALBEDO) return plan_fixed<kMatsNone, FRT_INTEGRATOR_ALBEDO, 5, 6, 6>(c, flags, L);
+    if (integrator == FRT_INTEGRATOR_DEPTH) return plan_fixed<kMatsNone, FRT_INTEGRATOR_DEPTH, 5, 6, 6>(c, flags, L);
     return FRT_E_INVALID;
 }

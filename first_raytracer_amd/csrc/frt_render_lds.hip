@@ -11,43 +11,36 @@
 #include "frt_kernels.hpp"
 #include "frt_plans.hpp"
 
-int frt_lds::path_oct(int stack, int waves, size_t scene_bytes, Launcher &L)
+// L = f(rung, scene bytes) on the octant rungs of the walk
+template <typename F>
+static int oct_rung(const frt_ctx *c, int flags, Launcher &L, F &&f)
 {
 #if defined(FRT_OCT_IN_MAIN)
     return FRT_E_UNSUPPORTED;
 #else
-    if (stack == 8) L = bvh_launcher<8, true, kWorldBvh2Oct, kMatsNone>(waves, scene_bytes);
-    else if (stack == 16) L = bvh_launcher<16, true, kWorldBvh2Oct, kMatsNone>(waves, scene_bytes);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
+    return walk_plan(c, flags, [&](auto r, size_t scene_bytes) -> int {
+        if constexpr (decltype(r)::world == kWorldBvh2Oct) {
+            L = f(r, scene_bytes);
+            return FRT_OK;
+        } else {
+            return FRT_E_UNSUPPORTED;
+        }
+    });
 #endif
 }
-// ... and with Russian roulette (FRT_FLAG_ROULETTE): one register cap, the default plan's 5 waves
-int frt_lds::path_oct_roulette(int stack, size_t scene_bytes, Launcher &L)
+int frt_lds::path_oct(const frt_ctx *c, int flags, int waves, Launcher &L)
 {
-#if defined(FRT_OCT_IN_MAIN)
-    return FRT_E_UNSUPPORTED;
-#else
-    if (stack == 8) L = make_launcher<8, kWorldBvh2Oct, true, 5, kMatsRoulette>(scene_bytes);
-    else if (stack == 16) L = make_launcher<16, kWorldBvh2Oct, true, 5, kMatsRoulette>(scene_bytes);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
-#endif
+    return oct_rung(c, flags, L, [&](auto r, size_t scene_bytes) {
+        return bvh_launcher<decltype(r)::stack, true, kWorldBvh2Oct, kMatsNone>(waves, scene_bytes);
+    });
 }
-// ... and with the Sobol' sampler (FRT_FLAG_SOBOL), with or without roulette: the same cap
-template <int MATS> static int path_oct_sobol_t(int stack, size_t scene_bytes, Launcher &L)
+// ... with Russian roulette (FRT_FLAG_ROULETTE), the Sobol' sampler (FRT_FLAG_SOBOL) or both: one
+// register cap, the default plan's 5 waves
+int frt_lds::path_oct_features(const frt_ctx *c, int flags, int features, Launcher &L)
 {
-    if (stack == 8) L = make_launcher<8, kWorldBvh2Oct, true, 5, MATS>(scene_bytes);
-    else if (stack == 16) L = make_launcher<16, kWorldBvh2Oct, true, 5, MATS>(scene_bytes);
-    else return FRT_E_UNSUPPORTED;
-    return FRT_OK;
-}
-int frt_lds::path_oct_sobol(int stack, bool roulette, size_t scene_bytes, Launcher &L)
-{
-#if defined(FRT_OCT_IN_MAIN)
-    return FRT_E_UNSUPPORTED;
-#else
-    return roulette ? path_oct_sobol_t<kMatsSobol | kMatsRoulette>(stack, scene_bytes, L)
-                    : path_oct_sobol_t<kMatsSobol>(stack, scene_bytes, L);
-#endif
+    return with_features(features, [&](auto x) -> int {
+        return oct_rung(c, flags, L, [&](auto r, size_t scene_bytes) {
+            return make_launcher<decltype(r)::stack, kWorldBvh2Oct, true, 5, decltype(x)::value>(scene_bytes);
+        });
+    });
 }

@@ -601,6 +601,28 @@ int frtx_selftest_trace_host(const frt_scene_view *scene, const float *rays, int
  * every slot is valid; out = n_slots x 3.  FRT_E_INVALID for n_chunks < 2 or counts that do not
  * describe such a cut. */
 int frtx_selftest_chunk_variance(const float *partial, int n_chunks, int64_t n_slots, int spp, int spi, float *out);
+/* The launch plan of a call, without a device: which kernel a render (kind 0: integrator, flags;
+ * FRT_INTEGRATOR_PSSMLT answers with its two kernels) or a ray query (kind 1: flags) would launch
+ * on a context whose uploaded scene has the properties in the query -- the fields the dispatch
+ * reads, nothing else.  env_sampling: the context's image has sampling tables (a render builds
+ * them on the device; the dispatch reads only that they exist).  The answer holds the dispatch's
+ * return code, the plan's fields and the kernel as the offset of its host-side handle from the
+ * library's load address: the value of that handle's symbol in the library's symbol table, whose
+ * name is the kernel's (0: no kernel).  The hook itself returns FRT_E_INVALID for a NULL
+ * argument, else FRT_OK. */
+typedef struct frt_plan_query {
+    int32_t kind, integrator, flags;
+    int32_t world_kind, stack_needed, has_bvh4, depth4;
+    int32_t mats, has_spec_mats, env_image, env_sampling, has_f64, precision;
+    int64_t scene_lds_bytes, scene_lds_bytes_oct;
+} frt_plan_query;
+typedef struct frt_plan_answer {
+    int32_t rc, stack, waves, lds_scene, wide, f64;
+    int64_t lds, scene_lds;
+    int64_t lds_boot;              /* PSS-MLT: the bootstrap launch's LDS bytes (lds: the chain launch's) */
+    uint64_t kernel, kernel_boot;  /* kernel_boot: PSS-MLT's bootstrap kernel (kernel: its chain kernel) */
+} frt_plan_answer;
+int frtx_selftest_plan(const frt_plan_query *q, frt_plan_answer *a);
 
 #ifdef __cplusplus
 }

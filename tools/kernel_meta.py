@@ -11,7 +11,8 @@ than one are listed on stderr).
   python tools/kernel_meta.py --diff parent.json new.json [--filter REGEX]
 
 --diff lists the kernels of the first file whose VGPR / AGPR / scratch / LDS /
-VGPR-spill figures or (where both files record one) instruction hash differ in
+VGPR-spill figures, (where both files record one) instruction hash or code
+objects (the translation units that hold the kernel, by link order) differ in
 the second, and counts the kernels only one has.
 A trailing `false` template argument that the second build added to the PSS-MLT
 kernels (mlt_bootstrap / mlt_megakernel <..., ENV = false>) is ignored when
@@ -151,6 +152,7 @@ def main():
             changed += 1
             continue
         gate = GATE + (("insn_hash",) if old[k].get("insn_hash") and by_old[k].get("insn_hash") else ())
+        gate += ("code_objects",)             # the units link in one order: the indices compare
         d = {x: (old[k].get(x), by_old[k].get(x)) for x in gate if old[k].get(x) != by_old[k].get(x)}
         if d:
             changed += 1
