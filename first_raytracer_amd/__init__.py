@@ -183,6 +183,18 @@ class TreeCost(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ShadowTreeInfo(ctypes.Structure):
+    """frt_shadow_tree_info: what the shadow-tree pass dropped and built, and what it saves."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("why", "kept_prims", "dropped_prims", "rule_a", "rule_b", "nodes_main",
+                                              "nodes_added", "nodes_shared", "root", "empty", "n_rays",
+                                              "root_stops_main", "root_stops_shadow", "n_nodes")] + [
+        (n, ctypes.c_double) for n in ("v_main", "t_main", "v_shadow", "t_shadow")] + [
+        ("segments", ctypes.c_int64), ("segment_hits", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PlanQuery(ctypes.Structure):
     """frt_plan_query: the scene properties and the call whose launch plan selftest_plan asks for."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kind", "integrator", "flags", "world_kind", "stack_needed", "has_bvh4",
@@ -220,7 +232,7 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_selftest_path_host_env")
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
 EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
-             "frtx_selftest_plan")
+             "frtx_selftest_plan", "frtx_selftest_shadow_tree")
 
 
 def lib():
@@ -290,6 +302,8 @@ def lib():
     L.frt_selftest_path_host_env.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp,
                                              ctypes.c_int, ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
     L.frtx_selftest_tree_refine.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(TreeCost), vp, vp, ctypes.c_int32]
+    L.frtx_selftest_shadow_tree.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(ShadowTreeInfo), vp, vp,
+                                            ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32]
     L.frtx_selftest_trace_host.argtypes = [ctypes.POINTER(SceneView), vp, ctypes.c_int64, vp]
     L.frtx_selftest_chunk_variance.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp]
     _lib = L
@@ -727,6 +741,21 @@ def selftest_tree_refine(scene):
     _check(lib().frtx_selftest_tree_refine(ctypes.byref(view), out, nodes[0].ctypes.data, nodes[1].ctypes.data, cap),
            "frtx_selftest_tree_refine")
     return tuple((out[k].as_dict(), nodes[k][:out[k].n_nodes].copy()) for k in range(2))
+
+
+def selftest_shadow_tree(scene, segments=0, seed=1):
+    """The counting hook of the shadow-tree pass: (info dict, dropped, nodes) -- the
+    frt_shadow_tree_info fields, one byte per scene-view triangle (1 = no area-light shadow
+    segment can hit it) and the flattened node records, the shadow tree's own behind the main
+    tree's nodes_main."""
+    view = scene.view()
+    cap = max(2 * int(view.n_nodes), 1) + 4
+    nodes = np.zeros((cap, 16), np.float32)
+    dropped = np.zeros(max(int(view.n_tris), 1), np.uint8)
+    out = ShadowTreeInfo()
+    _check(lib().frtx_selftest_shadow_tree(ctypes.byref(view), ctypes.byref(out), dropped.ctypes.data, nodes.ctypes.data,
+                                           cap, int(segments), int(seed)), "frtx_selftest_shadow_tree")
+    return out.as_dict(), dropped[:int(view.n_tris)].copy(), nodes[:out.n_nodes].copy()
 
 
 def selftest_trace_host(scene, rays):

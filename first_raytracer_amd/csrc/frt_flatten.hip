@@ -3,16 +3,20 @@
 // (BVH4Q), the octant node copies, the texel conversion and the topology
 // refinement of LDS-resident trees (refine_tree).  No kernel and no
 // HIP runtime call; built with the kernel units' compiler and flags so that
-// its floating-point results do not depend on which unit holds it.
+// its floating-point results do not depend on which unit holds it.  Also the
+// shadow-tree pass (shadow_tree): the occluder tree of area-light shadow rays
+// appended behind the main nodes.
 #include "frt_flatten.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 
 #include "frt_kernels.hpp"   // the LDS budgets (kLdsSceneBytes, kLdsOctBytes, kLdsMaxDepth, oct_lds_node_slots)
+#include "host/shadow_tree.hpp"
 #include "host/tree_refine.hpp"
 
 using namespace frt;
@@ -388,19 +392,20 @@ static void topology_of(const std::vector<float4> &nodes, frt_refine::Topology &
 }
 
 // the rays of one replayed frame against the leaves
+// occl (optional): per ray of R, 1 = an area-light shadow ray (light_shadow_ray)
 static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leaves, int frame, uint32_t seed,
-                        frt_refine::RaySet &R)
+                        frt_refine::RaySet &R, std::vector<uint8_t> *occl = nullptr, std::vector<float> *origins = nullptr)
 {
     const DevScene S = host_scene(F);
-    struct Ray { f3 o, d; float tmax; bool shadow; };
+    struct Ray { f3 o, d; float tmax; bool shadow, occl; };
     std::vector<Ray> rays;
     std::vector<int> stack(std::max(F.depth + 1, 1));
     for (int pix = 0; pix < frame * frame; ++pix) {
         PathState<float> P;
         path_begin<kMatsAll>(P, S, pix % frame, pix / frame, frame, frame, seed, (uint32_t)pix, 0u);
         for (;;) {
-            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow});
-            const Hit<float> h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow, light_shadow_ray(P)});
+            const Hit<float> h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), light_shadow_ray(P));
             uint32_t n_ext = 0, n_sh = 0;
             if (path_shade<kMatsAll>(P, S, h, kRefineMaxDepth, n_ext, n_sh)) break;
         }
@@ -419,6 +424,8 @@ static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leave
     }
     R.n_prims = (int)R.prim_ref.size();
     R.tmin.resize(n); R.tmax.resize(n); R.anyhit.resize(n); R.live.resize(n);
+    if (occl) occl->assign(n, 0);
+    if (origins) origins->clear();
     R.slab.resize((size_t)nl * n * 6);
     R.prim_t.resize((size_t)n * R.n_prims);
     // rays in a scattered order (a stride coprime to n), so that every chunk of the
@@ -433,6 +440,8 @@ static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leave
         R.tmin[i] = T.tmin;
         R.tmax[i] = q.tmax;
         R.anyhit[i] = q.shadow ? 1 : 0;
+        if (occl) (*occl)[i] = q.occl ? 1 : 0;
+        if (origins && q.occl) { origins->push_back(q.o.x); origins->push_back(q.o.y); origins->push_back(q.o.z); }
         const float inv[3] = {T.sr.invd.x, T.sr.invd.y, T.sr.invd.z}, oi[3] = {T.sr.oinv.x, T.sr.oinv.y, T.sr.oinv.z};
         for (int l = 0; l < nl; ++l) {
             float *s = &R.slab[((size_t)i * nl + l) * 6];
@@ -526,7 +535,197 @@ static bool refine_tree(FlatScene &F)
     return true;
 }
 
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine)
+// ---- the occluder tree of area-light shadow rays (DESIGN.md "Shadow tree") ----
+// path::Li's and pssmlt::Li's shadow rays to a light are segments from a surface
+// point to a point on a light.  host/shadow_tree.cpp proves for each triangle
+// whether any such segment can report a hit on it (in a closed room: the walls no
+// segment crosses, the light's own plane); the leaves that keep a primitive get a
+// binary tree of their own, built from the main tree's nodes where a subtree lost
+// nothing and appended behind them in F.nodes otherwise, and trav_begin starts
+// those rays at its root.  Every other ray, and BVH4Q, keep the main root.  A
+// shadow ray asks only whether a hit exists, so films and ray counts are
+// unchanged -- only visits drop.
+static bool shadow_tree_knob()
+{
+    const char *e = std::getenv("FRT_SHADOW_TREE");
+    return !(e && std::atoi(e) == 0);
+}
+
+// sv's triangles in device order (tri_view) for the proof, which names triangles as the leaves do
+static void shadow_tree(const frt_scene_view *sv, FlatScene &F)
+{
+    auto &I = F.shadow;
+    DevScene &S = F.meta;
+    I.nodes_main = (int)(F.nodes.size() / 4);
+    if (sv->n_lights <= 0) { I.why = FlatScene::kShadowNoLights; return; }
+    // dielectric and the specular lobes leave from p - eps n: only lambertian / diffuse_light scenes
+    for (int i = 0; i < sv->n_materials; ++i)
+        if (sv->materials[i].type != FRT_MAT_LAMBERTIAN && sv->materials[i].type != FRT_MAT_DIFFUSE_LIGHT) {
+            I.why = FlatScene::kShadowMaterial;
+            return;
+        }
+    if (!tree_in_lds(F) || F.nodes.empty()) { I.why = FlatScene::kShadowNotResident; return; }
+    const int nt = sv->n_tris;
+    std::vector<double> tv(9 * (size_t)nt), tn;
+    std::vector<uint8_t> smooth(nt, 0);
+    bool any_smooth = false;
+    for (int d = 0; d < nt; ++d) {
+        const int i = F.tri_view[d];
+        std::copy(&sv->tri_v[9 * (size_t)i], &sv->tri_v[9 * (size_t)i] + 9, &tv[9 * (size_t)d]);
+        smooth[d] = sv->tri_geometry_normal && !sv->tri_geometry_normal[i];
+        any_smooth |= smooth[d] != 0;
+    }
+    if (any_smooth) {
+        tn.resize(9 * (size_t)nt);
+        for (int d = 0; d < nt; ++d) std::copy(&sv->tri_n[9 * (size_t)F.tri_view[d]], &sv->tri_n[9 * (size_t)F.tri_view[d]] + 9, &tn[9 * (size_t)d]);
+    }
+    frt_shadow::Geometry g;
+    g.n_tris = nt; g.n_spheres = sv->n_spheres;
+    g.tri_v = tv.data(); g.tri_n = any_smooth ? tn.data() : nullptr; g.tri_smooth = smooth.data();
+    g.sphere = sv->sphere;
+    g.lights = F.lights.data(); g.n_lights = (int)F.lights.size(); g.sphere_bit = FRT_PRIM_SPHERE;
+    for (int k = 0; k < 3; ++k) { g.cam_o[k] = sv->cam_origin[k]; g.cam_u[k] = sv->cam_u[k]; g.cam_v[k] = sv->cam_v[k]; }
+    g.lens_r = sv->cam_lens_radius;
+    g.eps = (double)Cst<float>::eps;
+    frt_shadow::Classified c;
+    frt_shadow::classify(g, c);
+    if (c.why != frt_shadow::kRan) {
+        I.why = c.why == frt_shadow::kNoLights ? FlatScene::kShadowNoLights : FlatScene::kShadowTooLarge;
+        return;
+    }
+    // triangles outside the tree (trailing device ids) are in no leaf; count those in one
+    int n_dropped = 0;
+    for (int d = 0; d < nt; ++d) n_dropped += c.dropped[d];
+    if (n_dropped == 0) { I.why = FlatScene::kShadowNothing; return; }
+    std::vector<float> nodes(4 * F.nodes.size());
+    memcpy(nodes.data(), F.nodes.data(), sizeof(float4) * F.nodes.size());
+    frt_shadow::Tree t;
+    frt_shadow::build(nodes, S.root, c.dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
+    if (t.dropped_leaves == 0) { I.why = FlatScene::kShadowNothing; return; }
+    // the appended nodes must leave the scene on the plan it has (pick_launcher_t reads these sizes)
+    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
+    const int nn0 = I.nodes_main, nn1 = (int)(nodes.size() / 16);
+    const bool lds0 = sizeof(float4) * (4 * (size_t)nn0 + rest) <= kLdsSceneBytes;
+    const bool lds1 = sizeof(float4) * (4 * (size_t)nn1 + rest) <= kLdsSceneBytes;
+    const bool oct0 = !F.nodes_oct.empty();
+    const bool oct1 = sizeof(float4) * (oct_lds_node_slots(nn1) + rest) <= kLdsOctBytes;
+    if (lds0 != lds1 || oct0 != oct1) { I.why = FlatScene::kShadowBudget; return; }
+    F.nodes.resize((size_t)4 * nn1);
+    memcpy(F.nodes.data(), nodes.data(), sizeof(float) * nodes.size());
+    if (oct0) F.nodes_oct.resize(8 * F.nodes.size());
+    S.sroot = t.empty ? kSentinel : t.root;   // nothing can occlude: the traversal ends at its first step
+    I.why = FlatScene::kShadowRan;
+    I.dropped = c.dropped;
+    I.n_dropped = n_dropped; I.rule_a = c.n_rule_a; I.rule_b = c.n_rule_b;
+    I.added = t.added; I.shared = t.shared; I.empty = t.empty;
+}
+
+// every node of F.nodes -- the main tree and the shadow tree's own -- as one topology over the
+// distinct leaves; slot_of_ref(ref) names a root
+static void topology_all(const std::vector<float4> &nodes, frt_refine::Topology &t, std::vector<RefineLeaf> &leaves,
+                         std::vector<int> &leaf_refs)
+{
+    const int nn = (int)(nodes.size() / 4);
+    leaves.clear();
+    leaf_refs.clear();
+    for (int i = 0; i < nn; ++i)
+        for (int side = 0; side < 2; ++side) {
+            const float4 *n = &nodes[4 * i];
+            const int c = f2i(side ? n[3].y : n[3].x);
+            if (c >= 0 || std::find(leaf_refs.begin(), leaf_refs.end(), c) != leaf_refs.end()) continue;
+            const float b[2][6] = {{n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y}, {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w}};
+            RefineLeaf l;
+            for (int k = 0; k < 6; ++k) l.box[k] = b[side][k];
+            l.ref = c;
+            leaves.push_back(l);
+            leaf_refs.push_back(c);
+        }
+    t.n_leaves = (int)leaves.size();
+    t.root = t.n_leaves;
+    t.child.assign(2 * (size_t)nn, 0);
+    for (int i = 0; i < nn; ++i)
+        for (int side = 0; side < 2; ++side) {
+            const int c = f2i(side ? nodes[4 * i + 3].y : nodes[4 * i + 3].x);
+            t.child[2 * i + side] = c >= 0 ? t.n_leaves + c
+                                           : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), c) - leaf_refs.begin());
+        }
+}
+
+bool shadow_cost_host(const FlatScene &F, ShadowCost &out)
+{
+    out = ShadowCost{};
+    if (F.shadow.why != FlatScene::kShadowRan) return false;
+    frt_refine::Topology t;
+    std::vector<RefineLeaf> leaves;
+    std::vector<int> leaf_refs;
+    topology_all(F.nodes, t, leaves, leaf_refs);
+    frt_refine::RaySet R;
+    std::vector<uint8_t> occl;
+    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl);
+    const DevScene S = host_scene(F);
+    int n_occl = 0;
+    for (int i = 0; i < R.n; ++i) n_occl += occl[i];
+    out.n_rays = n_occl;
+    if (n_occl == 0) return true;
+    auto price = [&](int which) {   // V and T of the rays marked live, per area-light shadow ray
+        const frt_refine::Cost c = frt_refine::tree_cost(t, R);
+        out.V[which] = c.V * R.n / n_occl;
+        out.T[which] = c.T * R.n / n_occl;
+    };
+    // from the main root: the area-light shadow rays alone, those that miss the scene's box stopped there
+    for (int i = 0; i < R.n; ++i) {
+        R.live[i] = R.live[i] && occl[i];
+        if (occl[i] && !R.live[i]) ++out.stops[0];
+    }
+    price(0);
+    // from the shadow root.  trav_begin tests no box there, so every such ray is live; a ray that would
+    // miss the box of the shadow tree's leaves costs its one visit and is reported as a stop
+    if (F.shadow.empty) {   // kSentinel: done at the first step
+        out.stops[1] = n_occl;
+        return true;
+    }
+    const int sroot = S.sroot >= 0 ? t.n_leaves + S.sroot
+                                   : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), S.sroot) - leaf_refs.begin());
+    std::vector<int> under, st{sroot};   // the leaves under the shadow root
+    while (!st.empty()) {
+        const int s = st.back();
+        st.pop_back();
+        if (s < t.n_leaves) { under.push_back(s); continue; }
+        st.push_back(t.child[2 * (s - t.n_leaves)]);
+        st.push_back(t.child[2 * (s - t.n_leaves) + 1]);
+    }
+    auto misses_box = [&](int i) {   // the union of the leaves' slab records against trav_begin's interval
+        float u[6];
+        for (int k = 0; k < 6; ++k) u[k] = __builtin_inff();
+        for (int l : under)
+            for (int k = 0; k < 6; ++k) u[k] = std::min(u[k], R.slab[((size_t)i * R.n_leaves + l) * 6 + k]);
+        const float tn = std::max(std::max(u[0], u[1]), std::max(u[2], Cst<float>::eps));
+        const float tf = std::min(std::min(-u[3], -u[4]), std::min(-u[5], R.tmax[i]));
+        return !(tn <= tf);
+    };
+    R.root.assign(R.n, sroot);
+    for (int i = 0; i < R.n; ++i) {
+        R.live[i] = occl[i];
+        if (occl[i] && misses_box(i)) ++out.stops[1];
+    }
+    price(1);
+    return true;
+}
+
+void shadow_origins_host(const FlatScene &F, std::vector<float> &origins)
+{
+    origins.clear();
+    if (F.meta.world_kind != FRT_WORLD_BVH || F.nodes.empty()) return;
+    frt_refine::Topology t;
+    std::vector<RefineLeaf> leaves;
+    std::vector<int> leaf_refs;
+    topology_all(F.nodes, t, leaves, leaf_refs);
+    frt_refine::RaySet R;
+    std::vector<uint8_t> occl;
+    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl, &origins);
+}
+
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine, int shadow)
 {
     auto fail = [&](int code, const std::string &m) { err = m; return code; };
     const int nt = sv->n_tris, ns = sv->n_spheres, nm = sv->n_materials;
@@ -790,6 +989,7 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     if (sv->world_kind == FRT_WORLD_BVH && F.depth < kLdsMaxDepth && oct_bytes <= kLdsOctBytes)
         F.nodes_oct.resize(8 * F.nodes.size());
     S.root = (sv->world_kind == FRT_WORLD_BVH) ? ((sv->root >= 0) ? 0 : ~dev_ref(~sv->root)) : 0;
+    S.sroot = S.root;   // until the shadow-tree pass finds one
     // the trees derived from the binary nodes: the octant copies and BVH4Q
     auto derive_trees = [&]() {
         fill_octants(F);
@@ -825,7 +1025,14 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     S.lens_r64 = sv->cam_lens_radius;
     // topology refinement (refine_tree): needs the finished scene for its ray sample, so the
     // derived trees are made again from the nodes it rewrote
-    if ((refine < 0 ? tree_refine_knob() : refine != 0) && refine_tree(F)) derive_trees();
+    bool again = (refine < 0 ? tree_refine_knob() : refine != 0) && refine_tree(F);
+    // the shadow tree over the tree the main rays will walk: its nodes go behind the main ones
+    if (shadow < 0 ? shadow_tree_knob() : shadow != 0) {
+        shadow_tree(sv, F);
+        again |= F.shadow.why == FlatScene::kShadowRan;
+    }
+    if (again) derive_trees();
+    S.n_nodes = (int)(F.nodes.size() / 4);
     return FRT_OK;
 }
 

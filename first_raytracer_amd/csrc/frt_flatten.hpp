@@ -24,12 +24,29 @@ struct FlatScene {
     std::vector<int> tri_view;      // device triangle id -> scene-view triangle (DevScene::tri_view)
     DevScene meta{};     // scalars + camera; pointers filled by the consumer
     int depth = 0;
+    // what the shadow-tree pass did (frt_flatten.hip shadow_tree): why != kShadowRan leaves
+    // meta.sroot the main root and `nodes` untouched
+    enum { kShadowRan = 0, kShadowOff, kShadowNoLights, kShadowTooLarge, kShadowMaterial, kShadowNotResident,
+           kShadowNothing, kShadowBudget };
+    struct {
+        int why = kShadowOff;
+        std::vector<uint8_t> dropped;   // per device triangle
+        int n_dropped = 0, rule_a = 0, rule_b = 0, nodes_main = 0, added = 0, shared = 0;
+        bool empty = false;
+    } shadow;
 };
 
 // f64: also build the fp64 records of the fp64 kernels (DESIGN.md "Precision")
 // refine: the topology refinement of LDS-resident binary trees; -1 = as FRT_TREE_REFINE says
 // (default on, read at each call), 0 = off, 1 = on
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1);
+// shadow: the occluder tree of area-light shadow rays behind the main nodes, the same way (FRT_SHADOW_TREE)
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1, int shadow = -1);
+// V and T of the refinement pass's validation rays that are area-light shadow rays, started at the
+// main root (index 0) and at the shadow root (1); stops: how many of them miss that root's box
+struct ShadowCost { double V[2] = {0, 0}, T[2] = {0, 0}; int n_rays = 0, stops[2] = {0, 0}; };
+bool shadow_cost_host(const FlatScene &F, ShadowCost &out);
+// the origins of those rays (3 floats each), for the segment property test
+void shadow_origins_host(const FlatScene &F, std::vector<float> &origins);
 // traversal cost of F's binary tree on the refinement pass's validation rays (the counting
 // self-test); false when the tree is not LDS-resident, so the pass does not apply
 struct TreeCost { double V = 0.0, T = 0.0, J = 0.0, w = 0.0; int depth = 0, n_rays = 0; };

@@ -344,7 +344,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
         n_smp += started;
         // ---- set up the next ray's traversal (a scene miss is finished at once) ----
         if (next_ray) {
-            tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, ray_tmax());
+            // an area-light shadow ray starts at the shadow root (the environment-NEE ray has t_max = tmax)
+            const R tm = ray_tmax();
+            const bool occl = KIND == FRT_INTEGRATOR_PATH && P.shadow && ((MATS & kMatsEnvNee) == 0 || tm < R(1));
+            tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, tm, occl);
             pending = !tracing;
         }
         diag_t0 = FRT_DIAG_CLOCK();
@@ -486,7 +489,7 @@ struct MltWork {
 template <int WORLD, int STACK>
 __device__ __forceinline__ Hit<float> trace_any(const DevScene &S, const PathState<float> &P, int *stk)
 {
-    return trace<WORLD, kBlock, STACK>(S, P.ro, P.rd, P.rtmax, P.shadow, stk);
+    return trace<WORLD, kBlock, STACK>(S, P.ro, P.rd, P.rtmax, P.shadow, stk, P.shadow);   // pssmlt::Li: every shadow ray ends on a light
 }
 
 // bootstrap: sc of n_init independent eye paths (pssmlt.cpp:303-312); the host
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_EXP_
                         pending = true;
                     } else {
                         ext = true;
-                        tracing = trav_begin_world<WORLD>(T, S, M.P.ro, M.P.rd, M.P.rtmax);
+                        tracing = trav_begin_world<WORLD>(T, S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow);
                         pending = !tracing;
                     }
                 } else {
@@ -751,7 +754,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_EXP_
                 beyond = true;
                 pending = true;
             } else {
-                tracing = trav_begin_world<WORLD>(T, S, M.P.ro, M.P.rd, M.P.rtmax);
+                tracing = trav_begin_world<WORLD>(T, S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow);
                 pending = !tracing;
             }
         }

@@ -130,6 +130,9 @@ struct DevScene {
     int node_es, node_ps, tri_es, tri_ps, sh_es, sh_ps, node4_es, node4_ps;
     int n_nodes4;
     float root_lo[3], root_hi[3];
+    // root of the occluder tree of area-light shadow rays (flatten_scene's shadow tree; binary trees
+    // only): a node, ~leaf, or kSentinel when nothing can occlude.  The main root when the pass is off.
+    int sroot;
     float ao_tmax;           // ao.cpp:21 world box height * 0.5
     int ao_spheres_only;     // list world: ao.cpp's t_max is NaN (see ao_shade)
     f3 cam_o, cam_llc, cam_h, cam_v, cam_u, cam_vv, cam_w;
@@ -294,15 +297,25 @@ template <typename R> FRT_HD R bvh_tmin(V3<R> o)
 
 // Root box with the unscaled EPSILON (parallel_bvh.h:43), then bvh_tmin.
 // False: the ray misses the scene (T.h is the miss record).
-template <typename R> FRT_HD bool trav_begin(Trav<R> &T, const DevScene &S, int root, V3<R> o, V3<R> d, R tmax)
+// occl (binary trees): an area-light shadow ray, which starts at the shadow
+// tree's root -- the same answer, no triangle of the main tree that such a
+// segment cannot cross is visited (host/shadow_tree.cpp).  It skips the root
+// box test: that test only culls (a ray that misses the box misses both of the
+// root's child boxes, which lie inside it and are tested over a shorter
+// interval), a per-lane choice between two boxes held in SGPRs cost the Cornell
+// kernel 3.4 % (profiles/shadowtree), and on Cornell no shadow segment misses
+// the occluders' box anyway.
+template <typename R>
+FRT_HD bool trav_begin(Trav<R> &T, const DevScene &S, int root, V3<R> o, V3<R> d, R tmax, bool occl = false)
 {
     T.h = Hit<R>{-1, tmax, R(0), R(0)};
     T.sp = 0;
-    T.node = root;
+    T.node = occl ? S.sroot : root;
     T.sr = slab_ray(o, d);
     T.tmin = bvh_tmin(o);
-    return slab_entry<R>(S.root_lo[0], S.root_lo[1], S.root_lo[2], S.root_hi[0], S.root_hi[1], S.root_hi[2], T.sr,
-                         Cst<R>::eps, tmax) != R(__builtin_inff());
+    const bool in = slab_entry<R>(S.root_lo[0], S.root_lo[1], S.root_lo[2], S.root_hi[0], S.root_hi[1], S.root_hi[2], T.sr,
+                                  Cst<R>::eps, tmax) != R(__builtin_inff());
+    return occl || in;
 }
 
 // binary nodes: descend to a leaf, test it.  True when the query is finished.
@@ -522,10 +535,10 @@ FRT_HD bool bvh4_step(Trav<float> &T, const DevScene &S, f3 o, f3 d, bool anyhit
 }
 
 template <int STRIDE, typename R>
-FRT_HD Hit<R> trace_bvh(const DevScene &S, V3<R> o, V3<R> d, R tmax, bool anyhit, int *stk)
+FRT_HD Hit<R> trace_bvh(const DevScene &S, V3<R> o, V3<R> d, R tmax, bool anyhit, int *stk, bool occl = false)
 {
     Trav<R> T;
-    if (trav_begin(T, S, S.root, o, d, tmax))
+    if (trav_begin(T, S, S.root, o, d, tmax, occl))
         while (!bvh2_step<STRIDE>(T, S, o, d, anyhit, stk)) {}
     return T.h;
 }
@@ -598,23 +611,26 @@ template <typename R> FRT_HD Hit<R> trace_list(const DevScene &S, V3<R> o, V3<R>
     return h;
 }
 
+// occl: the ray is an area-light shadow ray (trav_begin); only the binary trees have a shadow root
 template <int WORLD, int STRIDE, int STACK = 0, typename R>
-FRT_HD Hit<R> trace(const DevScene &S, V3<R> o, V3<R> d, R tmax, bool anyhit, int *stk)
+FRT_HD Hit<R> trace(const DevScene &S, V3<R> o, V3<R> d, R tmax, bool anyhit, int *stk, bool occl = false)
 {
     if constexpr (WORLD == FRT_WORLD_LIST) return trace_list(S, o, d, tmax, anyhit);
     else if constexpr (WORLD == kWorldBvh4) return trace_bvh4<STRIDE, STACK, kBvh4Overflow>(S, o, d, tmax, anyhit, stk);
-    else return trace_bvh<STRIDE>(S, o, d, tmax, anyhit, stk);
+    else return trace_bvh<STRIDE>(S, o, d, tmax, anyhit, stk, occl);
 }
 
 // resumable form of trace<> (path_megakernel): begin, then steps until true
 template <int WORLD, typename R>
-FRT_HD bool trav_begin_world(Trav<R> &T, const DevScene &S, V3<R> o, V3<R> d, R tmax)
+FRT_HD bool trav_begin_world(Trav<R> &T, const DevScene &S, V3<R> o, V3<R> d, R tmax, bool occl = false)
 {
     if constexpr (WORLD == FRT_WORLD_LIST) {
         T.h = Hit<R>{-1, tmax, R(0), R(0)};
         return true;
+    } else if constexpr (WORLD == kWorldBvh4) {
+        return trav_begin(T, S, S.root4, o, d, tmax);
     } else {
-        return trav_begin(T, S, WORLD == kWorldBvh4 ? S.root4 : S.root, o, d, tmax);
+        return trav_begin(T, S, S.root, o, d, tmax, occl);
     }
 }
 template <int WORLD, int STRIDE, int STACK, int STEP = kStepBranch, typename R>
@@ -993,6 +1009,10 @@ FRT_HD void path_begin(PathState<R> &P, const DevScene &S, int px, int py, int n
     P.prev_p = zero3<R>();
     P.prev_spec = false;
 }
+
+// The ray P holds is an area-light shadow ray of path::Li / pssmlt::Li: a segment to a point on a
+// light (t_max below 1), not the environment-NEE ray (t_max = Cst::tmax).  Not for ao_shade's rays.
+template <typename R> FRT_HD bool light_shadow_ray(const PathState<R> &P) { return P.shadow && P.rtmax < R(1); }
 
 // Shadow ray done (path.cpp:50-77): add the NEE term if unoccluded, then the
 // extension ray.  The megakernel runs this inside its traversal loop, so

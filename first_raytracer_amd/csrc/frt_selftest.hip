@@ -30,13 +30,14 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
             ++cnt[0];
             for (;;) {
                 Hit<R> h;
+                const bool occl = p->integrator != FRT_INTEGRATOR_AO && light_shadow_ray(P);   // starts at the shadow root
                 if (S.world_kind == FRT_WORLD_LIST) {
                     h = trace<FRT_WORLD_LIST, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
                 } else if constexpr (!kIsF64<R>) {
                     h = wide ? trace<kWorldBvh4, 1, kSelftestStack>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data())
-                             : trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+                             : trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), occl);
                 } else {
-                    h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
+                    h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), occl);
                 }
                 n_ext = n_sh = 0;
                 const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade<MATS>(P, S, h, n_sh)
@@ -164,7 +165,7 @@ extern "C" int frt_selftest_mlt_paths_host(const frt_scene_view *sv, int nx, int
             if (mlt_beyond(M)) { M.P.L = M.P.L + M.P.beta * env_of<float>(S); break; }
             const Hit<float> h = (S.world_kind == FRT_WORLD_LIST)
                               ? trace<FRT_WORLD_LIST, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data())
-                              : trace<FRT_WORLD_BVH, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data());
+                              : trace<FRT_WORLD_BVH, 1>(S, M.P.ro, M.P.rd, M.P.rtmax, M.P.shadow, stack.data(), M.P.shadow);
             if (mlt_shade(M, S, h, src, ne, ns)) break;
         }
         const f3 L = M.P.L;
@@ -185,7 +186,7 @@ extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost
     for (int on = 0; on < 2; ++on) {
         FlatScene F;
         std::string err;
-        const int rc = flatten_scene(sv, F, err, false, on);
+        const int rc = flatten_scene(sv, F, err, false, on, 0);   // the main tree alone: no shadow-tree nodes behind it
         if (rc != FRT_OK) return rc;
         TreeCost c;
         const bool applies = tree_cost_host(F, c);
@@ -194,6 +195,64 @@ extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost
         if (dst[on]) {
             if (nn > max_nodes) return FRT_E_INVALID;
             memcpy(dst[on], F.nodes.data(), F.nodes.size() * sizeof(float4));
+        }
+    }
+    return FRT_OK;
+}
+
+// Counting hook of the shadow-tree pass (frt_flatten.hip shadow_tree): what it dropped and built,
+// the traversal cost of the area-light shadow rays from either root, and the segment property test
+extern "C" int frtx_selftest_shadow_tree(const frt_scene_view *sv, frt_shadow_tree_info *out, uint8_t *dropped,
+                                         float *nodes, int32_t max_nodes, int64_t segments, uint32_t seed)
+{
+    if (!sv || !out || segments < 0) return FRT_E_INVALID;
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false, -1, 1);
+    if (rc != FRT_OK) return rc;
+    const auto &I = F.shadow;
+    memset(out, 0, sizeof(*out));
+    out->why = I.why;
+    out->n_nodes = (int)(F.nodes.size() / 4);
+    out->nodes_main = I.nodes_main;
+    out->root = F.meta.sroot;
+    if (nodes) {
+        if (out->n_nodes > max_nodes) return FRT_E_INVALID;
+        memcpy(nodes, F.nodes.data(), F.nodes.size() * sizeof(float4));
+    }
+    if (dropped) memset(dropped, 0, (size_t)std::max(sv->n_tris, 0));
+    if (I.why != FlatScene::kShadowRan) return FRT_OK;
+    out->dropped_prims = I.n_dropped;
+    out->kept_prims = sv->n_tris + sv->n_spheres - I.n_dropped;
+    out->rule_a = I.rule_a; out->rule_b = I.rule_b;
+    out->nodes_added = I.added; out->nodes_shared = I.shared; out->empty = I.empty ? 1 : 0;
+    if (dropped)
+        for (int d = 0; d < sv->n_tris; ++d) dropped[F.tri_view[d]] = I.dropped[d];
+    ShadowCost c;
+    shadow_cost_host(F, c);
+    out->n_rays = c.n_rays;
+    out->v_main = c.V[0]; out->t_main = c.T[0]; out->v_shadow = c.V[1]; out->t_shadow = c.T[1];
+    out->root_stops_main = c.stops[0]; out->root_stops_shadow = c.stops[1];
+    if (segments > 0) {
+        std::vector<float> org;
+        shadow_origins_host(F, org);
+        const DevScene S = host_scene(F);
+        const int64_t no = (int64_t)(org.size() / 3);
+        for (int64_t i = 0; i < segments && no > 0 && S.n_lights > 0; ++i) {
+            const RngKey key = rng_key(seed, (uint32_t)i, (uint32_t)(i >> 32));
+            const float *q = &org[3 * (size_t)(i % no)];
+            const f3 o = mk3(q[0], q[1], q[2]);
+            int idx = (int)(rng_u(key, 0) * (float)S.n_lights);
+            if (idx == S.n_lights) idx -= 1;
+            f3 ln;
+            int lmat;
+            const f3 d = prim_sample(S, S.lights[idx], o, rng_u(key, 1), rng_u(key, 2), ln, lmat);
+            ++out->segments;
+            for (int t = 0; t < S.n_tris; ++t) {
+                if (!I.dropped[t]) continue;
+                float u, v;
+                if (prim_t(S, t, o, d, bvh_tmin(o), 1.0f - Cst<float>::shadow_eps, u, v) > 0.0f) ++out->segment_hits;
+            }
         }
     }
     return FRT_OK;

@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 #include "frt.h"
 
@@ -49,7 +51,7 @@ void count_rays(const Topology &t, const RaySet &R, const Tables &tb, const int 
         const bool any = R.anyhit[r] != 0;
         const float *pt = &R.prim_t[(size_t)r * R.n_prims];
         float tb_ = R.tmax[r];
-        int hp = -1, sp = 0, node = t.root;
+        int hp = -1, sp = 0, node = R.root.empty() ? t.root : R.root[r];
         int stk[kMaxLevels];
         for (;;) {
             while (node >= L) {   // interior node: bvh2_step's visit
@@ -94,23 +96,33 @@ void count_rays(const Topology &t, const RaySet &R, const Tables &tb, const int 
 
 void build_tables(const Topology &t, const RaySet &R, Tables &tb)
 {
-    const int L = t.n_leaves, nI = std::max(L - 1, 0);
+    const int L = t.n_leaves, nI = (int)(t.child.size() / 2);
     tb.n_slots = L + nI;
     tb.tab.resize((size_t)R.n * tb.n_slots * 6);
-    // children before parents: the reverse of a pre-order walk
-    std::vector<int> order, st{t.root};
+    // children before parents: a post-order walk from every root a ray starts at (a second root may
+    // share subtrees with the first, so a node is taken once)
+    std::vector<int> order, roots{t.root};
+    roots.insert(roots.end(), R.root.begin(), R.root.end());
+    std::sort(roots.begin(), roots.end());
+    roots.erase(std::unique(roots.begin(), roots.end()), roots.end());
+    std::vector<char> seen(tb.n_slots, 0);
+    std::vector<std::pair<int, bool>> st;   // (slot, children done)
+    for (int root : roots) st.push_back({root, false});
     while (!st.empty()) {
-        const int s = st.back();
+        const auto [s, done] = st.back();
         st.pop_back();
         if (s < L) continue;
-        order.push_back(s);
-        st.push_back(t.child[2 * (s - L)]);
-        st.push_back(t.child[2 * (s - L) + 1]);
+        if (done) { order.push_back(s); continue; }
+        if (seen[s]) continue;
+        seen[s] = 1;
+        st.push_back({s, true});
+        st.push_back({t.child[2 * (s - L)], false});
+        st.push_back({t.child[2 * (s - L) + 1], false});
     }
     for (int r = 0; r < R.n; ++r) {
         float *base = &tb.tab[(size_t)r * tb.n_slots * 6];
         memcpy(base, &R.slab[(size_t)r * L * 6], sizeof(float) * 6 * L);
-        for (size_t k = order.size(); k-- > 0;) {
+        for (size_t k = 0; k < order.size(); ++k) {
             const int s = order[k], j = s - L;
             unite(base + 6 * t.child[2 * j], base + 6 * t.child[2 * j + 1], base + 6 * s);
         }

@@ -21,10 +21,14 @@ struct RaySet {
     std::vector<int> prim_first;            // [leaf], n_leaves + 1 entries: the leaf's primitives in prim_*
     std::vector<int> prim_ref;              // [prim]: device ref (FRT_PRIM_SPHERE bit for a sphere)
     std::vector<float> prim_t;              // [ray][prim]: the primitive's hit distance within the ray's interval, or -1
+    std::vector<int> root;                  // [ray]: the slot the ray's traversal starts at (`live`: its box is passed);
+                                            // empty: every ray starts at the tree's root
 };
 
 // Binary tree over leaves 0 .. n_leaves - 1.  A node ref is a "slot": a leaf
-// index, or n_leaves + the interior node's index; n_leaves - 1 interior nodes.
+// index, or n_leaves + the interior node's index; n_leaves - 1 interior nodes
+// -- more when a second root (RaySet::root) shares subtrees with the first, which
+// tree_cost prices and refine does not take.
 struct Topology {
     int n_leaves = 0, root = 0;
     std::vector<int> child;                 // [2 * interior]: the two child slots

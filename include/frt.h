@@ -591,6 +591,29 @@ typedef struct frt_tree_cost {
 } frt_tree_cost;
 int frtx_selftest_tree_refine(const frt_scene_view *scene, frt_tree_cost out[2], float *nodes_off, float *nodes_on,
                              int32_t max_nodes);
+/* The counting hook of the shadow-tree pass (FRT_SHADOW_TREE, README): the scene is flattened with
+ * the pass on, whatever the environment says.  why: 0 the pass ran, 1 switched off, 2 no lights,
+ * 3 coordinates too large for the proof, 4 a material other than lambertian / diffuse_light, 5 the
+ * binary tree is not LDS-resident, 6 nothing to drop, 7 the extra nodes would change the launch plan.
+ * With why = 0: the primitives kept and dropped (by the half-space rule, by the lights'-plane rule),
+ * the main tree's nodes, the nodes appended and the main nodes the shadow tree shares, its root
+ * (node index, or ~leaf) and whether it is empty; v_* / t_*: node visits and primitive tests per
+ * area-light shadow ray of the refinement pass's validation rays (n_rays of them) started at the
+ * main root and at the shadow root, root_stops_*: how many miss that root's box (the kernels test
+ * no box at the shadow root: there such a ray costs the one visit that v_shadow counts).  segments > 0:
+ * that many segments from those rays' origins to seeded points on the lights are put to the fp32
+ * tri_intersect of every dropped triangle over (t_min, 1 - shadow_eps]; segment_hits counts the
+ * hits, which the proof says is 0.  dropped: n_tris bytes per scene-view triangle, nodes: the
+ * flattened node records as frtx_selftest_tree_refine gives them (NULL to skip either). */
+typedef struct frt_shadow_tree_info {
+    int32_t why, kept_prims, dropped_prims, rule_a, rule_b;
+    int32_t nodes_main, nodes_added, nodes_shared, root, empty;
+    int32_t n_rays, root_stops_main, root_stops_shadow, n_nodes;
+    double v_main, t_main, v_shadow, t_shadow;
+    int64_t segments, segment_hits;
+} frt_shadow_tree_info;
+int frtx_selftest_shadow_tree(const frt_scene_view *scene, frt_shadow_tree_info *out, uint8_t *dropped, float *nodes,
+                              int32_t max_nodes, int64_t segments, uint32_t seed);
 /* frt_trace_device's queries through the same code on the host (host memory,
  * the same ray and hit layout), over the scene flattened as an upload would
  * flatten it (FRT_TREE_REFINE and FRT_LEAF_SIZE are read) */
