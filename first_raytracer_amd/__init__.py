@@ -232,7 +232,7 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_selftest_path_host_env")
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
 EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
-             "frtx_selftest_plan", "frtx_selftest_shadow_tree")
+             "frtx_selftest_plan", "frtx_selftest_shadow_tree", "frtx_render_pixels", "frtx_render_pixels_device")
 
 
 def lib():
@@ -306,6 +306,9 @@ def lib():
                                             ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32]
     L.frtx_selftest_trace_host.argtypes = [ctypes.POINTER(SceneView), vp, ctypes.c_int64, vp]
     L.frtx_selftest_chunk_variance.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp]
+    L.frtx_render_pixels.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, ctypes.POINTER(Stats)]
+    L.frtx_render_pixels_device.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, vp,
+                                            ctypes.POINTER(Stats)]
     _lib = L
     return L
 
@@ -530,18 +533,42 @@ class Context:
         p.integrator = FRT_INTEGRATOR_ERROR
         return self.render(p)
 
-    def render_until(self, params, target, max_spp, first_spp=16):
+    def render_pixels(self, params, pixels, variance=True):
+        """frtx_render_pixels: the pixels of the list (linear indices y * nx + x of the frame of
+        `params`; duplicates allowed) through the sparse kernel -- per entry the mean of the
+        samples [sample_offset, sample_offset + spp) that render() draws for that pixel, and the
+        batch-means V of render_error over chunks of samples_per_item samples (0: spp / 16).
+        path and ao.  Leaves the chunk sums of the last render() alone.
+        Returns (rgb (n, 3) float32, V (n, 3) float32 or None, stats)."""
+        pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+        rgb = np.zeros((len(pixels), 3), np.float32)
+        V = np.zeros((len(pixels), 3), np.float32) if variance else None
+        st = Stats()
+        _check(lib().frtx_render_pixels(self.ptr, ctypes.byref(params), pixels.ctypes.data, len(pixels), rgb.ctypes.data,
+                                        V.ctypes.data if variance else None, ctypes.byref(st)),
+               "frtx_render_pixels", self.ptr)
+        return rgb, V, st
+
+    def render_until(self, params, target, max_spp, first_spp=None, adaptive=False, switch=None):
         """Progressive render of `params` (path or ao; spp and sample_offset are the driver's) that
         stops at a requested error instead of a guessed sample count.  The frame figure is
         e = sqrt(mean V) / mean film (frame_error): the predicted RMSE of the film over its mean.
-        Pass 0 renders first_spp samples (a power of two >= 2), each later pass as many as there
-        are so far; the film is accumulated with film_accumulate and V combined with
+        Pass 0 renders first_spp samples (a power of two >= 2; None: 16, or ADAPTIVE_FIRST_SPP for
+        an adaptive run), each later pass as many as there are so far; the film is accumulated with film_accumulate and V combined with
         combine_variance (the passes are independent).  The loop ends when e <= target (converged)
         or when the next pass would exceed max_spp.  With FRT_FLAG_SOBOL the samples of a pixel
         are one net and V says nothing about its error: four replicates (seeds seed .. seed + 3)
         are each extended by the same passes, the film is their mean and V the sample variance
         of the four replicate means / 4 (replicate_variance); spp_used counts all four.
-        Returns (film, V, spp_used, e, converged)."""
+        Returns (film, V, spp_used, e, converged).
+        adaptive=True: the later passes sample only the pixels whose own error is above the
+        target (render_until's rule; render_pixels when their share is below `switch`);
+        returns (film, V, counts, e, converged) with counts the (ny, nx) int32 samples per pixel."""
+        if adaptive:
+            film, V, counts, e, ok, _ = render_until(lambda p: self.render(p), lambda p: self.render_error(p)[0],
+                                                     params, target, max_spp, first_spp, adaptive=True,
+                                                     render_pixels=lambda p, px: self.render_pixels(p, px), switch=switch)
+            return film, V, counts, e, ok
         film, V, spp, e, ok, _ = render_until(lambda p: self.render(p), lambda p: self.render_error(p)[0],
                                               params, target, max_spp, first_spp)
         return film, V, spp, e, ok
@@ -630,14 +657,52 @@ def replicate_variance(films):
     return mean, v.astype(np.float32)
 
 
-def render_until(render, render_error, params, target, max_spp, first_spp=16):
+# The active share of the frame below which an adaptive pass goes through render_pixels: the
+# full render's time over the sparse kernel's for the same pixels and samples, rounded down to
+# one decimal (1080p, 64 spp, one MI355X: profiles/adaptive/switch.json).
+ADAPTIVE_SWITCH = 0.5
+# The first pass of an adaptive run when the caller names none: the smallest power of two at which
+# the run's sum of mean V stays inside the calibration window of the sum of the actual squared
+# error (tools/adaptive_calibration.py, profiles/adaptive/calibration.json)
+ADAPTIVE_FIRST_SPP = 128
+
+
+def frame_mean(film):
+    """Mean of all 3 nx ny film values, added one after the other in float64 (np.cumsum adds in
+    order): the sum frt::render_until's adaptive rule forms, bit for bit."""
+    f = np.asarray(film, np.float64).reshape(-1)
+    return float(np.cumsum(f)[-1] / f.size)
+
+
+def render_until(render, render_error, params, target, max_spp, first_spp=None, adaptive=False, render_pixels=None,
+                 switch=None):
     """The loop of Context.render_until over callables: render(params) -> (film, stats) and
     render_error(params) -> V of the render just done.  Returns (film, V, spp_used, e,
     converged, passes) with passes = [(spp_used, e, kernel ms of the pass)].
     A pass whose render cut the samples into one chunk (stats.work_items equals the slot
     count; the granule depends on the device, so it is seen only after the render) has no
     spread to estimate from: it is rendered again with samples_per_item = half the pass --
-    that pass is paid twice -- and every later pass asks for half-pass granules up front."""
+    that pass is paid twice -- and every later pass asks for half-pass granules up front.
+
+    adaptive=True (render_pixels(params, pixels) -> (rgb, V, stats) of the listed pixels): after
+    every pass tau = target x the film's mean (frame_mean), and a pixel is active while the mean
+    of its three V exceeds tau^2, i.e. sqrt(mean_c V) > tau.  Pass 0 is the full render of
+    first_spp samples; a later pass gives every active pixel as many samples as it has (n for
+    the most-sampled one), from the first sample index not yet handed out -- so sample_offset =
+    spp = n while the active pixels share one count -- through render_pixels when the active
+    share of the frame is below `switch` (default ADAPTIVE_SWITCH), else through the full render
+    of n samples, after which every pixel holds the new samples.  Per pixel the film merges as film_accumulate and V as
+    combine_variance, with that pixel's own count.  The loop ends when no pixel is active --
+    then mean V <= tau^2 and e <= target -- or when the next pass would take an active pixel
+    past max_spp (2 n > max_spp).  A pixel that stops on its own V is biased: pixels whose first
+    samples happen to agree stop early with a V that is too small, so the run's e is optimistic
+    unless first_spp is large (DESIGN.md 5d has the measured size; hence ADAPTIVE_FIRST_SPP).  FRT_FLAG_SOBOL is
+    refused: V is an upper estimate there and the replicates give no per-pixel figure.
+    Returns (film, V, counts, e, converged, passes): counts the (ny, nx) int32 samples per
+    pixel, passes = [(samples over the frame so far, e, kernel ms, pixels the pass sampled,
+    whether it went through render_pixels)]."""
+    if first_spp is None:        # 16; an adaptive run: ADAPTIVE_FIRST_SPP
+        first_spp = ADAPTIVE_FIRST_SPP if adaptive else 16
     first_spp, max_spp = int(first_spp), int(max_spp)
     if first_spp < 2 or first_spp & (first_spp - 1):
         raise FrtError("render_until: first_spp must be a power of two >= 2")
@@ -652,6 +717,14 @@ def render_until(render, render_error, params, target, max_spp, first_spp=16):
     slots = lib().frt_shard_slot_count(ctypes.byref(params))
     if slots < 0:
         raise FrtError("bad render params")
+    if adaptive:
+        if sobol:
+            raise FrtError("render_until: adaptive with FRT_FLAG_SOBOL is refused -- V is an upper estimate under "
+                           "Sobol' points and the replicates give no per-pixel error; render without the flag")
+        if render_pixels is None:
+            raise FrtError("render_until: adaptive needs a render_pixels callable")
+        return _render_until_adaptive(render, render_error, render_pixels, params, float(target), max_spp, first_spp,
+                                      slots, ADAPTIVE_SWITCH if switch is None else float(switch))
     films, V, total, passes = [None] * reps, None, 0, []
     halve = False
     while True:
@@ -683,6 +756,72 @@ def render_until(render, render_error, params, target, max_spp, first_spp=16):
             return film, V, reps * total, e, True, passes
         if reps * 2 * total > max_spp:
             return film, V, reps * total, e, False, passes
+
+
+def _render_until_adaptive(render, render_error, render_pixels, params, target, max_spp, first_spp, slots, switch):
+    nx, ny = params.nx, params.ny
+    npx = nx * ny
+    halve = False
+
+    def full_pass(n, offset):
+        nonlocal halve
+        p = RenderParams.from_buffer_copy(params)
+        p.spp, p.sample_offset = n, offset
+        if halve:
+            p.samples_per_item = n // 2
+        film, st = render(p)
+        if st.work_items == slots:        # one chunk a pixel
+            halve = True
+            p.samples_per_item = n // 2
+            film, st = render(p)
+        return film, np.asarray(render_error(p), np.float32), st.kernel_ms
+
+    def merge(film_px, V_px, cnt_px, rgb, Vp, n):
+        # (k, 3) values of k pixels: one film_accumulate / combine_variance per distinct count
+        for c in np.unique(cnt_px):
+            g = cnt_px == c
+            film_px[g] = film_accumulate(film_px[g], int(c), rgb[g], n)
+            V_px[g] = combine_variance(int(c), V_px[g], n, Vp[g])
+
+    film, V, ms = full_pass(first_spp, 0)
+    film = np.array(film, np.float32).reshape(npx, 3)
+    V = np.array(V, np.float32).reshape(npx, 3)
+    counts = np.full(npx, first_spp, np.int64)
+    offset = first_spp                    # samples [0, offset) of a pixel's stream are handed out
+    passes, sampled, sparse = [], npx, False
+    while True:
+        tau = target * frame_mean(film)
+        v64 = V.astype(np.float64)
+        active = np.flatnonzero(((v64[:, 0] + v64[:, 1]) + v64[:, 2]) / 3.0 > tau * tau)
+        e = frame_error(film, V)
+        passes.append((int(counts.sum()), e, ms, sampled, sparse))
+        done = len(active) == 0
+        n = 0 if done else int(counts[active].max())      # the pass to come doubles the active pixels
+        if done or 2 * n > max_spp:
+            return (film.reshape(ny, nx, 3), V.reshape(ny, nx, 3), counts.astype(np.int32).reshape(ny, nx), e, done,
+                    passes)
+        sparse = len(active) < switch * npx
+        if sparse:
+            # one call per count among the active pixels, each doubling its group: after sparse
+            # passes alone that is one call with sample_offset = spp = n; a pixel that stopped
+            # and is active again (tau moves with the film's mean) doubles its smaller count
+            ms, before = 0.0, counts[active]
+            for c in np.unique(before):
+                idx = active[before == c]
+                p = RenderParams.from_buffer_copy(params)
+                p.spp, p.sample_offset, p.samples_per_item = int(c), offset, 0
+                rgb, Vp, st = render_pixels(p, idx.astype(np.int32))
+                ms += st.kernel_ms
+                film[idx] = film_accumulate(film[idx], int(c), np.asarray(rgb, np.float32), int(c))
+                V[idx] = combine_variance(int(c), V[idx], int(c), np.asarray(Vp, np.float32))
+                counts[idx] += c
+            sampled = len(active)
+        else:
+            rgb, Vp, ms = full_pass(n, offset)
+            merge(film, V, counts, np.asarray(rgb, np.float32).reshape(npx, 3), Vp.reshape(npx, 3), n)
+            counts += n
+            sampled = npx
+        offset += n
 
 
 def selftest_chunk_variance(partial, spp, spi):

@@ -70,6 +70,13 @@ struct frt_ctx {
     std::vector<ncclComm *> comms;   // ncclComm_t (frt_multi.hip)
     float *gather = nullptr; size_t gather_bytes = 0;
     float *film_dev = nullptr; size_t film_dev_bytes = 0;
+    // frtx_render_pixels (frt_render_sparse.hip): buffers of its own -- the chunk sums, the
+    // per-wave ray counters, and the host call's device copies of the list and the outputs --
+    // so that `partial` and last_render still describe the last full render
+    float *sp_partial = nullptr; size_t sp_partial_bytes = 0;
+    unsigned long long *sp_wave_rays = nullptr; size_t sp_wave_rays_bytes = 0;
+    int32_t *sp_pixels = nullptr; size_t sp_pixels_bytes = 0;
+    float *sp_out = nullptr; size_t sp_out_bytes = 0;
 };
 
 #pragma GCC visibility push(hidden)
@@ -116,6 +123,10 @@ inline Residency residency(const frt_ctx *c, int flags)
 int eff_tile(const frt_render_params *p);
 bool params_ok(const frt_render_params *p);
 int render_impl(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats);
+int trav_min(bool lds_scene, bool path = false);
+int min_desc(bool lds_scene);
+bool use_f64(const frt_ctx *c, const frt_render_params *p);
+int env_tables(frt_ctx *c);
 // frt_multi.hip
 void free_comms(frt_ctx *c);
 // frt_denoise.hip: the filter of FRT_INTEGRATOR_DENOISE over a whole frame in slot order (shard 0

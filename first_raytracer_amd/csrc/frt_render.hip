@@ -147,6 +147,10 @@ extern "C" int frt_destroy(frt_ctx *c)
     free_comms(c);
     if (c->gather) (void)hipFree(c->gather);
     if (c->film_dev) (void)hipFree(c->film_dev);
+    if (c->sp_partial) (void)hipFree(c->sp_partial);
+    if (c->sp_wave_rays) (void)hipFree(c->sp_wave_rays);
+    if (c->sp_pixels) (void)hipFree(c->sp_pixels);
+    if (c->sp_out) (void)hipFree(c->sp_out);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -196,7 +200,7 @@ extern "C" int frt_internal_lbvh(frt_ctx *c, int n, const float *box6, int32_t *
 // cheaper LDS node loop moved the LDS path optimum to 20 (Cornell 245.3 ->
 // 242.5 ms; 16 / 24: 243.4 / 243.7; profiles/r04/r04{h,i}/ab_*.jsonl).
 // FRT_TRAV_MIN overrides (tuning knob of this library, not part of the C-ABI).
-static int trav_min(bool lds_scene, bool path = false)
+int trav_min(bool lds_scene, bool path)
 {
     const char *e = std::getenv("FRT_TRAV_MIN");
     const int v = e ? std::atoi(e)
@@ -209,7 +213,7 @@ static int trav_min(bool lds_scene, bool path = false)
 // HBM plans 12 since round 4 (cornell_1m 512 spp 767.5 -> 760.9 ms over 8, 16:
 // 761.6, same call, profiles/r04/r04n; confirmed 765.4 -> 759.2 in r04o).
 // FRT_MIN_DESC overrides (tuning knob, not part of the C-ABI).
-static int min_desc(bool lds_scene)
+int min_desc(bool lds_scene)
 {
     const char *e = std::getenv("FRT_MIN_DESC");
     const int v = e ? std::atoi(e) : (lds_scene ? kMinDescLds : kMinDescHbm);
@@ -268,7 +272,7 @@ extern "C" int frt_set_env_image(frt_ctx *c, const frt_image *img)
 // FRT_FLAG_ENV_SAMPLING: the context's image has its sampling tables behind the
 // texels.  Built here, on the host from the texels the kernels read, at the first
 // render that wants them; no render in flight reads that part of the buffer.
-static int env_tables(frt_ctx *c)
+int env_tables(frt_ctx *c)
 {
     if (c->env_tab != frt_ctx::kEnvTabNone) return FRT_OK;
     const size_t n = (size_t)c->env_nx * c->env_ny;
@@ -395,7 +399,7 @@ extern "C" int frt_shard_slots(const frt_render_params *p, int32_t *slot_pixel)
 
 // does this render run the fp64 kernels?  FRT_FLAG_FP64 / _FP32 override the
 // context's precision for one call (A/B)
-static bool use_f64(const frt_ctx *c, const frt_render_params *p)
+bool use_f64(const frt_ctx *c, const frt_render_params *p)
 {
     if (p->integrator != FRT_INTEGRATOR_PATH || (p->flags & FRT_FLAG_FP32)) return false;
     if (p->flags & FRT_FLAG_FP64) return true;

@@ -1,0 +1,499 @@
+// frt_render_sparse.hip -- frtx_render_pixels / frtx_render_pixels_device (frt.h): a list of
+// pixels rendered by a persistent kernel of its own, and the reduction of its chunk sums to the
+// mean and the batch-means variance (frt_error.hpp).  The per-lane code is the megakernel's
+// (path_begin, trav_begin_world / trav_step_world, shade_kind / path_after_shadow) with the
+// megakernel's RNG streams, so a listed pixel gets the samples frt_render draws for it.  No
+// existing kernel, DevWork or plan is touched: the adaptive drivers (render_until) spend their
+// later passes through this unit.
+//
+// Kernels.  Rungs: walk_plan with HBM residency forced -- the list world, the binary tree at
+// stacks 16 / 32 / 64, the 4-wide tree; fp64 as plan_f64 has it (list, binary 32 / 64).  The scene
+// is always read from HBM: a sparse pass is small and an LDS copy is a fixed cost per block.
+// Material sets: collapsed to {none, all} as the host replay (frt_selftest.hip) collapses them --
+// the sets of the full dispatch times these rungs would be over 150 kernels.  A path render takes
+//   kMatsNone                          a lambertian scene, no image, no estimator flag
+//   kMatsAll [| kMatsEnv [| kMatsEnvNee]] | feature bits     every other case
+// and AO kMatsAll [| kMatsEnv], as in the full render: 114 kernels.  No register cap (the
+// compiler's own allocation).  The whole unit is built with the basic SGPR register allocator,
+// like frt_render_mats.hip (Makefile; DESIGN.md "Register-cap hazard").
+//
+// The unit compiles in parts (FRT_SPARSE_PART, Makefile) so that the parts build side by side:
+// 0 = the C-ABI, the reduce kernel, the lambertian and AO kernels; 1, 2, 3 = the path kernels of
+// kMatsAll, kMatsAll | kMatsEnv, and the sampled image.  Without the macro it is one unit.
+#undef FRT_DIAG
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "frt_kernels.hpp"
+#include "frt_plans.hpp"
+#include "frt_error.hpp"
+
+#ifdef FRT_SPARSE_PART
+#define FRT_SPARSE_HAS(k) (FRT_SPARSE_PART == (k))
+#else
+#define FRT_SPARSE_HAS(k) 1
+#endif
+
+#pragma GCC visibility push(hidden)
+namespace frt_sparse {
+struct SparseLauncher {
+    const void *fn = nullptr;
+    size_t lds = 0;
+    int stack = 0;
+    bool wide = false, f64 = false;
+};
+// the path kernels of the material sets with every material, one function a part
+int pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // part 1
+int pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);   // part 2
+int pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // part 3
+}  // namespace frt_sparse
+#pragma GCC visibility pop
+using frt_sparse::SparseLauncher;
+
+namespace {
+
+constexpr int kSparseCounterWord = 48;   // the context's queue words (kCounterBytes): 0 render, 32 ray queries, 48 this unit
+
+// the work of one call: items are (64-entry block of the list, chunk), block-major, so a refill
+// hands adjacent list entries to the lanes of a wave and a pixel's chunks run close in time
+struct SparseWork {
+    int nx, ny, spp, max_depth;
+    uint32_t seed, s_off;
+    int spi, n_chunks;
+    uint32_t npix, npad, n_items;        // list entries, ... padded to 64, npad * n_chunks
+    int trav_min, min_desc;
+    const int32_t *pixels;               // [npix] linear pixel y * nx + x
+    float *partial;                      // [n_chunks][npad][3]; padding entries are never written
+    unsigned *counter;
+    unsigned long long *wave_rays;       // [n_waves][4]: camera, extension, shadow, samples
+    uint32_t grab;
+};
+
+// The unit's two kernels stand in a namespace named after the film_reduce family.  The plan
+// table's test (tests/test_plans_host.py) sorts every kernel of the library by the first name of
+// its qualified name into the families that frtx_selftest_plan's dispatch chooses from
+// (path_megakernel, trace_kernel, the PSS-MLT pair: each must be a row of tests/golden/plans.json)
+// and a fixed list of families that no such plan chooses, film_reduce among them.  These kernels
+// have a dispatch of their own (sparse_plan below) and are no rows of that table, so they are
+// declared under the second kind; their own names stay sparse_kernel and sparse_reduce, which
+// is what a profile shows.
+namespace film_reduce {
+// path_megakernel's loop (frt_kernels.hpp) over a pixel list: the per-sample plan (a sample's
+// radiance is summed in P.L and rounded into the item's fp32 sum when the sample ends), the
+// scene from HBM, the item state and the stack columns in LDS
+template <int STACK, int WORLD, int MATS, int KIND, typename R>
+__global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const SparseWork W)
+{
+    extern __shared__ __attribute__((aligned(16))) int lds_mem[];
+    int *stk = lds_mem + threadIdx.x;
+    constexpr int kStackInts = WORLD != FRT_WORLD_LIST ? STACK * kBlock : 0;
+    DevScene S = S0;
+    scene_strides_hbm(S);
+    const int lane = threadIdx.x & 63;
+    bool have_item = false, exhausted = false, active = false;
+    uint32_t q_cur = 0, q_end = 0;
+    const ItemState I{lds_mem + kStackInts + (int)threadIdx.x};
+    PathState<R> P;
+    Trav<R> T;
+    bool tracing = false, pending = false;
+    int ovf[kOverflow<WORLD>];
+    unsigned long long n_cam = 0, n_ext = 0, n_sh = 0, n_smp = 0;
+    for (;;) {
+        for (;;) {
+            bool shadow_done = false;
+            if (tracing && trav_step_world<WORLD, kBlock, STACK, kPathStep<KIND>>(T, S, P.ro, P.rd, P.shadow, stk, ovf,
+                                                                                  W.min_desc)) {
+                if (KIND == FRT_INTEGRATOR_PATH && P.shadow) {
+                    if (path_after_shadow<MATS>(P, T.h.prim < 0)) {
+                        shadow_done = true;
+                        tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, P.rtmax);
+                        pending = !tracing;
+                    } else {
+                        tracing = false;
+                        pending = true;
+                    }
+                } else {
+                    tracing = false;
+                    pending = true;
+                }
+            }
+            n_ext += __popcll(__ballot(shadow_done));
+            if (__popcll(__ballot(tracing)) <= W.trav_min) break;
+        }
+        uint32_t ne = 0, ns = 0;
+        bool next_ray = false;
+        if (pending) {
+            pending = false;
+            const bool done = shade_kind<KIND, MATS>(P, S, T.h, W.max_depth, ne, ns);
+            if (done) {
+                I.set(kIsAcc + 0, f2i(i2f(I.get(kIsAcc + 0)) + (float)P.L.x));
+                I.set(kIsAcc + 1, f2i(i2f(I.get(kIsAcc + 1)) + (float)P.L.y));
+                I.set(kIsAcc + 2, f2i(i2f(I.get(kIsAcc + 2)) + (float)P.L.z));
+            }
+            active = !done;
+            next_ray = !done;
+        }
+        n_ext += __popcll(__ballot(ne != 0));
+        n_sh += __popcll(__ballot(ns != 0));
+        // a finished item: its chunk sum goes to its own (chunk, entry) element
+        if (!active && have_item && I.get(kIsCur) >= I.get(kIsEnd)) {
+            float *dst = W.partial + 3ull * ((size_t)(uint32_t)I.get(kIsChunk) * W.npad + (uint32_t)I.get(kIsSlot));
+            dst[0] = i2f(I.get(kIsAcc + 0)); dst[1] = i2f(I.get(kIsAcc + 1)); dst[2] = i2f(I.get(kIsAcc + 2));
+            have_item = false;
+        }
+        // wave-aggregated refill (path_megakernel): the wave's own range first, then one atomic
+        const bool need = !active && !have_item && !exhausted;
+        const uint64_t m = __ballot(need);
+        if (m) {
+            const uint32_t nm = (uint32_t)__popcll(m), r = lane_rank(m);
+            const uint32_t left = q_end - q_cur;
+            uint32_t w;
+            if (nm <= left) {
+                w = q_cur + r;
+                q_cur += nm;
+            } else {
+                const uint32_t take = max(W.grab, nm - left);
+                const int leader = __ffsll((unsigned long long)m) - 1;
+                uint32_t base = 0;
+                if (lane == leader) base = atomicAdd(W.counter, take);
+                base = __shfl(base, leader);
+                w = r < left ? q_cur + r : base + (r - left);
+                q_cur = base + (nm - left);
+                q_end = base + take;
+            }
+            if (need) {
+                if (w >= W.n_items) {
+                    exhausted = true;
+                } else {
+                    const uint32_t q = w >> 6;
+                    const uint32_t chunk = q % (uint32_t)W.n_chunks;
+                    const uint32_t entry = (q / (uint32_t)W.n_chunks) * 64u + (w & 63u);
+                    if (entry < W.npix) {   // padding entries of the last block carry no work
+                        have_item = true;
+                        const int pix = W.pixels[entry];
+                        const int s_cur = (int)chunk * W.spi;
+                        I.set(kIsCur, s_cur);
+                        I.set(kIsSlot, (int)entry);
+                        I.set(kIsChunk, (int)chunk);
+                        I.set(kIsPix, pix);
+                        I.set(kIsEnd, min(W.spp, s_cur + W.spi));
+                        I.set(kIsPx, pix % W.nx);
+                        I.set(kIsPy, pix / W.nx);
+                        I.set(kIsAcc + 0, 0); I.set(kIsAcc + 1, 0); I.set(kIsAcc + 2, 0);
+                    }
+                }
+            }
+        }
+        const bool start = !active && have_item && I.get(kIsCur) < I.get(kIsEnd);
+        if (start) {
+            const int s_cur = I.get(kIsCur);
+            path_begin<MATS>(P, S, I.get(kIsPx), I.get(kIsPy), W.nx, W.ny, W.seed, (uint32_t)I.get(kIsPix),
+                             (uint32_t)s_cur + W.s_off);
+            I.set(kIsCur, s_cur + 1);
+            active = true;
+            next_ray = true;
+        }
+        const unsigned long long started = __popcll(__ballot(start));
+        n_cam += started;
+        n_smp += started;
+        if (next_ray) {
+            // an area-light shadow ray starts at the shadow root (the environment-NEE ray has t_max = tmax)
+            const bool occl = KIND == FRT_INTEGRATOR_PATH && P.shadow && ((MATS & kMatsEnvNee) == 0 || P.rtmax < R(1));
+            tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, P.rtmax, occl);
+            pending = !tracing;
+        }
+        if (__ballot(active || !exhausted) == 0) break;
+    }
+    const unsigned long long c[4] = {n_cam, n_ext, n_sh, n_smp};
+    if (lane == 0) {
+        const size_t wv = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+        for (int k = 0; k < 4; ++k) W.wave_rays[4 * wv + k] = c[k];
+    }
+}
+
+}  // namespace film_reduce
+
+template <int STACK, int WORLD, int MATS, int KIND, typename R>
+SparseLauncher make_sparse()
+{
+    SparseLauncher L;
+    L.fn = reinterpret_cast<const void *>(&film_reduce::sparse_kernel<STACK, WORLD, MATS, KIND, R>);
+    L.lds = (WORLD != FRT_WORLD_LIST ? (size_t)STACK * kBlock * sizeof(int) : 0) + (size_t)kItemWords * kBlock * sizeof(int);
+    L.stack = STACK;
+    L.wide = WORLD == kWorldBvh4;
+    L.f64 = kIsF64<R>;
+    return L;
+}
+
+// the rung of the context's scene with the scene in HBM
+template <int MATS, int KIND>
+int sparse_plan(const frt_ctx *c, int flags, bool f64, SparseLauncher &L)
+{
+    if (f64) {   // plan_f64's rungs
+        if constexpr (KIND == FRT_INTEGRATOR_PATH) {
+            if (c->world_kind == FRT_WORLD_LIST) L = make_sparse<16, FRT_WORLD_LIST, MATS, KIND, double>();
+            else if (c->stack_needed < 32) L = make_sparse<32, FRT_WORLD_BVH, MATS, KIND, double>();
+            else if (c->stack_needed < 64) L = make_sparse<64, FRT_WORLD_BVH, MATS, KIND, double>();
+            else return FRT_E_UNSUPPORTED;
+            return FRT_OK;
+        } else {
+            return FRT_E_UNSUPPORTED;
+        }
+    }
+    return walk_plan(c, flags | FRT_FLAG_NO_LDS_SCENE, [&](auto r, size_t) -> int {
+        using Rg = decltype(r);
+        if constexpr (Rg::lds) {
+            return FRT_E_UNSUPPORTED;   // not reached: the flag forces HBM residency
+        } else {
+            L = make_sparse<Rg::stack, Rg::world, MATS, KIND, float>();
+            return FRT_OK;
+        }
+    });
+}
+template <int BASE>
+int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
+{
+    switch (features) {
+    case 0: return sparse_plan<BASE, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    case kMatsRoulette: return sparse_plan<BASE | kMatsRoulette, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    case kMatsSobol: return sparse_plan<BASE | kMatsSobol, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    default: return sparse_plan<BASE | kMatsSobol | kMatsRoulette, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    }
+}
+
+}  // namespace
+
+#if FRT_SPARSE_HAS(1)
+int frt_sparse::pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
+{
+    return sparse_plan_features<kMatsAll>(c, flags, f64, features, L);
+}
+#endif
+#if FRT_SPARSE_HAS(2)
+int frt_sparse::pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
+{
+    return sparse_plan_features<kMatsAll | kMatsEnv>(c, flags, f64, features, L);
+}
+#endif
+#if FRT_SPARSE_HAS(3)
+int frt_sparse::pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
+{
+    return sparse_plan_features<kMatsAll | kMatsEnv | kMatsEnvNee>(c, flags, f64, features, L);
+}
+#endif
+
+#if FRT_SPARSE_HAS(0)
+namespace {
+
+namespace film_reduce {   // see sparse_kernel
+// entry i of the list: mean = sum over chunks (fixed order) * (1 / spp), film_reduce's arithmetic,
+// and V per channel through frt_error.hpp.  Entries i >= npix (padding) are never read.
+__global__ __launch_bounds__(256) void sparse_reduce(const float *__restrict__ partial, float *__restrict__ out_rgb,
+                                                     float *__restrict__ out_var, uint32_t npix, uint32_t npad, int n_chunks,
+                                                     int spp, int spi)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    float sum[3] = {0.0f, 0.0f, 0.0f};
+    ChunkVar a[3];
+    for (int c = 0; c < n_chunks; ++c) {
+        const float *q = partial + 3ull * ((size_t)c * npad + i);
+        const float x[3] = {q[0], q[1], q[2]};
+        sum[0] += x[0]; sum[1] += x[1]; sum[2] += x[2];
+        if (out_var) {
+            const float n = chunk_samples(c, n_chunks, spp, spi), r = chunk_ratio(c, n_chunks, spp, spi);
+            chunk_var_add(a[0], x[0], n, r); chunk_var_add(a[1], x[1], n, r); chunk_var_add(a[2], x[2], n, r);
+        }
+    }
+    const float k = 1.0f / (float)spp;
+    for (int ch = 0; ch < 3; ++ch) {
+        out_rgb[3ull * i + ch] = sum[ch] * k;
+        if (out_var) out_var[3ull * i + ch] = chunk_var_result(a[ch], n_chunks, spp);
+    }
+}
+
+}  // namespace film_reduce
+
+int pick_sparse(const frt_ctx *c, int integrator, int flags, bool f64, bool env_sampling, SparseLauncher &L)
+{
+    const bool env = c->env_texels != nullptr;
+    if (integrator == FRT_INTEGRATOR_AO)
+        return env ? sparse_plan<kMatsAll | kMatsEnv, FRT_INTEGRATOR_AO>(c, flags, false, L)
+                   : sparse_plan<kMatsAll, FRT_INTEGRATOR_AO>(c, flags, false, L);
+    const int features = ((flags & FRT_FLAG_ROULETTE) ? kMatsRoulette : 0) | ((flags & FRT_FLAG_SOBOL) ? kMatsSobol : 0);
+    if (env_sampling) return frt_sparse::pick_nee(c, flags, f64, features, L);
+    if (env) return frt_sparse::pick_all_env(c, flags, f64, features, L);
+    if (c->mats != kMatsNone || features) return frt_sparse::pick_all(c, flags, f64, features, L);
+    return sparse_plan<kMatsNone, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+}
+
+template <typename T>
+int grow(frt_ctx *c, T *&buf, size_t &have, size_t bytes)
+{
+    bytes = std::max<size_t>(bytes, 16);
+    if (bytes <= have) return FRT_OK;
+    if (buf) HIPCHK(c, hipFree(buf));
+    buf = nullptr;
+    have = 0;
+    HIPCHK(c, hipMalloc((void **)&buf, bytes));
+    have = bytes;
+    return FRT_OK;
+}
+
+// what can be refused without a context or a device: the request and the list (host memory)
+int check_request(frt_ctx *c, const frt_render_params *p, const int32_t *pixels_host, int64_t npix, int *spi, int *n_chunks,
+                  bool want_var)
+{
+    if (!p || npix < 0) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
+    const int k = p->integrator;
+    if (k == FRT_INTEGRATOR_NORMALS || k == FRT_INTEGRATOR_ALBEDO || k == FRT_INTEGRATOR_DEPTH)
+        return set_err(c, FRT_E_UNSUPPORTED, "render_pixels: path and ao only (normals, albedo and depth have no sparse kernel)");
+    if (k != FRT_INTEGRATOR_PATH && k != FRT_INTEGRATOR_AO)
+        return set_err(c, FRT_E_INVALID, "render_pixels: path and ao only (pssmlt is no per-pixel estimator; denoise and error "
+                                         "are films of a whole frame)");
+    if (p->shard_count != 1)
+        return set_err(c, FRT_E_INVALID, "render_pixels: shard_count must be 1 (split the list instead)");
+    frt_render_params q = *p;
+    q.tile_size = 0;   // ignored here
+    if (!params_ok(&q)) return set_err(c, FRT_E_INVALID, "bad render params");
+    *spi = p->samples_per_item > 0 ? std::min(p->samples_per_item, p->spp) : std::max(1, p->spp / 16);
+    *n_chunks = (p->spp + *spi - 1) / *spi;
+    if (want_var && *n_chunks < 2)
+        return set_err(c, FRT_E_INVALID, "render_pixels: the variance needs at least 2 chunks a pixel; pass samples_per_item "
+                                         "< spp (e.g. spp / 2)");
+    if (pixels_host) {
+        const int64_t n = (int64_t)p->nx * p->ny;
+        for (int64_t i = 0; i < npix; ++i)
+            if (pixels_host[i] < 0 || pixels_host[i] >= n)
+                return set_err(c, FRT_E_INVALID, "render_pixels: entry " + std::to_string(i) + " is pixel " +
+                                                     std::to_string(pixels_host[i]) + ", outside [0, nx * ny)");
+    }
+    return FRT_OK;
+}
+
+// the list, the outputs: device memory; the request is checked
+int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, int spi, int n_chunks,
+                float *out_rgb, float *out_var, hipStream_t st, frt_stats *stats)
+{
+    const auto t_start = std::chrono::steady_clock::now();
+    bool env_sampling = false;
+    if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator == FRT_INTEGRATOR_PATH && c->env_texels) {
+        if (const int trc = env_tables(c)) return trc;
+        env_sampling = c->env_tab == frt_ctx::kEnvTabBuilt;
+    }
+    if (p->integrator == FRT_INTEGRATOR_AO && c->has_metal)
+        return set_err(c, FRT_E_UNSUPPORTED, "ao integrator: metal has no sampling pdf (constant_pdf::generate)");
+    const bool f64 = use_f64(c, p);
+    if (f64 && !c->has_f64)
+        return set_err(c, FRT_E_INVALID, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
+                                         "before frt_upload_scene");
+    SparseLauncher L;
+    if (pick_sparse(c, p->integrator, p->flags, f64, env_sampling, L) != FRT_OK || !L.fn)
+        return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
+    int bpc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, L.fn, kBlock, L.lds) != hipSuccess || bpc <= 0) bpc = 1;
+    const uint64_t npad = ((uint64_t)npix + 63) & ~63ull;
+    const uint64_t n_items = npad * (uint64_t)n_chunks;
+    const int grid = (int)std::min<uint64_t>((uint64_t)c->n_cu * bpc, (n_items + kBlock - 1) / kBlock);
+    const size_t n_waves = (size_t)grid * kBlock / 64;
+    const uint32_t grab = kQueueGrab;
+    // the 32-bit queue head runs past n_items by at most one grab per wave (render_impl's check)
+    if (n_items + (uint64_t)n_waves * (grab + 64) >= 0xffffffffULL)
+        return set_err(c, FRT_E_UNSUPPORTED, "render_pixels: list too long for one call: split it");
+    if (const int rc = grow(c, c->sp_partial, c->sp_partial_bytes, (size_t)n_items * 3 * sizeof(float))) return rc;
+    if (const int rc = grow(c, c->sp_wave_rays, c->sp_wave_rays_bytes, n_waves * 4 * sizeof(unsigned long long))) return rc;
+    SparseWork W{};
+    W.nx = p->nx; W.ny = p->ny; W.spp = p->spp; W.max_depth = p->max_depth; W.seed = p->seed;
+    W.s_off = (uint32_t)p->sample_offset;
+    W.spi = spi; W.n_chunks = n_chunks;
+    W.npix = (uint32_t)npix; W.npad = (uint32_t)npad; W.n_items = (uint32_t)n_items;
+    W.trav_min = trav_min(false, p->integrator == FRT_INTEGRATOR_PATH);
+    W.min_desc = min_desc(false);
+    W.pixels = pixels; W.partial = c->sp_partial;
+    W.counter = c->counter + kSparseCounterWord;   // a queue word of its own
+    W.wave_rays = c->sp_wave_rays;
+    W.grab = grab;
+    HIPCHK(c, hipMemsetAsync(W.counter, 0, sizeof(unsigned), st));
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    DevScene Sarg = c->S;
+    void *args[] = {&Sarg, &W};
+    const hipError_t le = hipLaunchKernel(L.fn, dim3(grid), dim3(kBlock), args, L.lds, st);
+    if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("sparse_kernel launch: ") + hipGetErrorString(le));
+    hipLaunchKernelGGL(film_reduce::sparse_reduce, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, c->sp_partial, out_rgb, out_var,
+                       W.npix, W.npad, n_chunks, p->spp, spi);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    std::vector<unsigned long long> wr(n_waves * 4);
+    HIPCHK(c, hipMemcpyAsync(wr.data(), c->sp_wave_rays, wr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        for (size_t w = 0; w < n_waves; ++w) {
+            stats->camera_rays += wr[4 * w]; stats->extension_rays += wr[4 * w + 1];
+            stats->shadow_rays += wr[4 * w + 2]; stats->samples += wr[4 * w + 3];
+        }
+        stats->pixels = (uint64_t)npix;
+        stats->work_items = (uint64_t)npix * n_chunks;
+        stats->stack_entries = (uint32_t)L.stack;
+        stats->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
+        stats->scene_bytes = c->scene_lds_bytes;
+        stats->kernel_ms = ms;
+        stats->fp64 = L.f64 ? 1u : 0u;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return FRT_OK;
+}
+
+}  // namespace
+
+extern "C" int frtx_render_pixels_device(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                                         float *out_rgb, float *out_var, void *hip_stream, frt_stats *st)
+{
+    int spi = 0, n_chunks = 0;
+    if (const int rc = check_request(c, p, nullptr, npix, &spi, &n_chunks, out_var != nullptr)) return rc;
+    if (!c) return FRT_E_INVALID;
+    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+    if (st) memset(st, 0, sizeof(*st));
+    if (npix == 0) return FRT_OK;
+    if (!pixels || !out_rgb) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the list is read back and checked before any kernel runs
+    std::vector<int32_t> host((size_t)npix);
+    HIPCHK(c, hipMemcpyAsync(host.data(), pixels, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    if (const int rc = check_request(c, p, host.data(), npix, &spi, &n_chunks, out_var != nullptr)) return rc;
+    return sparse_impl(c, p, pixels, npix, spi, n_chunks, out_rgb, out_var, stream, st);
+}
+
+extern "C" int frtx_render_pixels(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, float *out_rgb,
+                                  float *out_var, frt_stats *st)
+{
+    int spi = 0, n_chunks = 0;
+    if (npix > 0 && !pixels) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
+    if (const int rc = check_request(c, p, pixels, npix, &spi, &n_chunks, out_var != nullptr)) return rc;
+    if (!c) return FRT_E_INVALID;
+    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+    if (st) memset(st, 0, sizeof(*st));
+    if (npix == 0) return FRT_OK;
+    if (!out_rgb) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n3 = (size_t)npix * 3;
+    if (const int rc = grow(c, c->sp_pixels, c->sp_pixels_bytes, (size_t)npix * sizeof(int32_t))) return rc;
+    if (const int rc = grow(c, c->sp_out, c->sp_out_bytes, 2 * n3 * sizeof(float))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->sp_pixels, pixels, (size_t)npix * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const int rc = sparse_impl(c, p, c->sp_pixels, npix, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
+                               c->stream, st);
+    if (rc != FRT_OK) return rc;
+    HIPCHK(c, hipMemcpy(out_rgb, c->sp_out, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIPCHK(c, hipMemcpy(out_var, c->sp_out + n3, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+#endif  // part 0

@@ -5,7 +5,7 @@
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
 //              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals|albedo|depth] [--chains 262144]
 //              [--denoise [--denoise-spp 16]]
-//              [--error-out v.pfm] [--target-error E --max-spp N [--first-spp 16]]
+//              [--error-out v.pfm] [--target-error E --max-spp N [--first-spp 16] [--adaptive [--switch S]]]
 //              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
@@ -21,6 +21,12 @@
 // --target-error E --max-spp N: frt::render_until -- passes of --first-spp, then doubling, until
 //   e <= E or the next pass would exceed N samples per pixel; --ns is ignored; one line per pass
 //   with the total spp, e and the pass's kernel ms.  With --sobol four replicates give the error.
+// --adaptive (with --target-error): later passes sample only the pixels whose own error is above the
+//   target (frt::render_until's adaptive rule), through frtx_render_pixels on the first GPU when their
+//   share of the frame is below --switch (default frt::kAdaptiveSwitch); --first-spp defaults to
+//   frt::kAdaptiveFirstSpp there; one line per pass with the
+//   samples over the frame, the pixels sampled and how; --counts-out writes the samples per pixel as
+//   PFM.  Not with --sobol.
 // --env: constant environment colour (the reference scenes' is black).
 // --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
 //   image_texture, material.h:206-244); exclusive with --env.
@@ -56,7 +62,9 @@ int main(int argc, char **argv)
     double target_error = 0.0;
     long max_spp = 0;
     int first_spp = 16;
-    bool has_target = false, has_max_spp = false, has_first_spp = false;
+    bool has_target = false, has_max_spp = false, has_first_spp = false, adaptive = false;
+    double switch_share = frt::kAdaptiveSwitch;
+    std::string counts_out;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -88,6 +96,9 @@ int main(int argc, char **argv)
         else if (a == "--target-error") { target_error = std::atof(next()); has_target = true; }
         else if (a == "--max-spp") { max_spp = std::atol(next()); has_max_spp = true; }
         else if (a == "--first-spp") { first_spp = std::atoi(next()); has_first_spp = true; }
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--switch") switch_share = std::atof(next());
+        else if (a == "--counts-out") counts_out = next();
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -117,6 +128,13 @@ int main(int argc, char **argv)
     }
     if ((until || !error_out.empty()) && integrator != "path" && integrator != "ao") {
         std::fprintf(stderr, "--error-out / --target-error: only a path or ao render has an error film\n");
+        return 2;
+    }
+    if (adaptive && !has_first_spp) first_spp = frt::kAdaptiveFirstSpp;
+    if (adaptive && !until) { std::fprintf(stderr, "--adaptive goes with --target-error\n"); return 2; }
+    if (!counts_out.empty() && !adaptive) { std::fprintf(stderr, "--counts-out goes with --adaptive\n"); return 2; }
+    if (adaptive && sobol) {
+        std::fprintf(stderr, "--adaptive and --sobol exclude each other (no per-pixel error under Sobol' points)\n");
         return 2;
     }
     if (until && max_spp <= 0) { std::fprintf(stderr, "--target-error needs --max-spp\n"); return 2; }
@@ -153,7 +171,16 @@ int main(int argc, char **argv)
                 const frt::until_result r = frt::render_until(set, render.params(nx, ny, first_spp), target_error, max_spp, first_spp,
                                                               [](long spp, double e, double ms) {
                                                                   std::printf("pass: %ld spp  e = %.6g  %.3f ms\n", spp, e, ms);
-                                                              });
+                                                              }, adaptive, switch_share);
+                for (const frt::until_pass &ps : r.passes)
+                    std::printf("adaptive pass: %lld samples  %ld pixels %s  e = %.6g  %.3f ms\n", ps.samples, ps.sampled,
+                                ps.sparse ? "sparse" : "full", ps.e, ps.ms);
+                if (!counts_out.empty()) {
+                    std::vector<float> cf((size_t)nx * ny * 3);
+                    for (size_t i = 0; i < r.counts.size(); ++i) cf[3 * i] = cf[3 * i + 1] = cf[3 * i + 2] = (float)r.counts[i];
+                    frt::check(frt_write_pfm(counts_out.c_str(), nx, ny, cf.data()), "frt_write_pfm");
+                    std::printf("Saved %s\n", counts_out.c_str());
+                }
                 std::printf("%s after %ld spp: e = %.6g (target %.6g)\n", r.converged ? "Converged" : "Not converged",
                             r.spp_used, r.e, target_error);
                 film.store_film(r.film.data());

@@ -646,6 +646,30 @@ typedef struct frt_plan_answer {
     uint64_t kernel, kernel_boot;  /* kernel_boot: PSS-MLT's bootstrap kernel (kernel: its chain kernel) */
 } frt_plan_answer;
 int frtx_selftest_plan(const frt_plan_query *q, frt_plan_answer *a);
+/* Render a list of pixels (not in the reference; the adaptive drivers' later passes).  Entry i
+ * of `pixels` is a linear pixel y * nx + x of the nx x ny frame of `p`; out_rgb[3i .. 3i + 2] is
+ * the mean radiance of its samples [sample_offset, sample_offset + spp): the samples frt_render
+ * draws for that pixel with the same seed, max_depth, flags and environment, so the value is the
+ * full render's up to fp32 summation order.  out_var (NULL to skip): the batch-means estimate V
+ * of FRT_INTEGRATOR_ERROR for that entry, over chunks of samples_per_item samples (0: the library
+ * takes max(1, spp / 16)); with out_var and fewer than 2 chunks the call is FRT_E_INVALID (the
+ * text names samples_per_item).  Integrators: FRT_INTEGRATOR_PATH and _AO (normals, albedo,
+ * depth: FRT_E_UNSUPPORTED; pssmlt, denoise, error: FRT_E_INVALID).  Precision as in frt_render
+ * (the context's, FRT_FLAG_FP64 / _FP32); FRT_FLAG_ENV_SAMPLING, _ROULETTE and _SOBOL as in
+ * frt_render; FRT_FLAG_BVH2 selects the binary tree; the other plan flags do nothing -- a kernel
+ * of its own reads the scene from HBM -- and tile_size is ignored.  shard_count must be 1.  A
+ * pixel outside [0, nx * ny) is FRT_E_INVALID before any kernel runs.  Duplicates are allowed,
+ * each entry is rendered on its own; npix = 0 returns FRT_OK and writes nothing.  The call uses
+ * buffers of its own: the chunk sums of the context's last frt_render stay, and a
+ * FRT_INTEGRATOR_ERROR call after it still describes that render.  st: the three ray counters,
+ * samples = npix * spp, pixels = npix, work_items, kernel_ms (both kernels), stack_entries,
+ * bvh_depth, fp64; scene_in_lds = 0.
+ * frtx_render_pixels: list and outputs in host memory.  frtx_render_pixels_device: all three in
+ * device memory, launched on hip_stream (NULL: the context's); returns when the work is done. */
+int frtx_render_pixels(frt_ctx *ctx, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                       float *out_rgb, float *out_var, frt_stats *st);
+int frtx_render_pixels_device(frt_ctx *ctx, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                              float *out_rgb, float *out_var, void *hip_stream, frt_stats *st);
 
 #ifdef __cplusplus
 }

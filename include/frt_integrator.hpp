@@ -6,6 +6,7 @@
 // reads the same against frt::renderer<frt::path_gpu>.  Errors become
 // exceptions (frt::error), as the reference throws std::runtime_error.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -368,12 +369,41 @@ inline void replicate_variance(const std::vector<float> r[4], std::vector<float>
     }
 }
 
+struct until_pass {
+    long long samples = 0;   // over the frame, after the pass
+    double e = 0.0, ms = 0.0;
+    long sampled = 0;        // pixels the pass sampled
+    bool sparse = false;     // through frtx_render_pixels
+};
 struct until_result {
     std::vector<float> film, variance;   // nx x ny x 3 each, the film's order
-    long spp_used = 0;
+    long spp_used = 0;                   // adaptive: the largest count of a pixel
     double e = 0.0;
     bool converged = false;
+    std::vector<int32_t> counts;         // adaptive: samples per pixel, nx x ny
+    std::vector<until_pass> passes;      // adaptive
 };
+
+// frtx_render_pixels (frt.h) on one context: the listed pixels' means and, with `variance`, their V
+inline frt_stats render_pixels(frt_ctx *ctx, const frt_render_params &p, const std::vector<int32_t> &pixels,
+                               std::vector<float> &rgb, std::vector<float> *variance = nullptr)
+{
+    rgb.assign(pixels.size() * 3, 0.0f);
+    if (variance) variance->assign(pixels.size() * 3, 0.0f);
+    frt_stats st{};
+    check(frtx_render_pixels(ctx, &p, pixels.data(), (int64_t)pixels.size(), rgb.data(), variance ? variance->data() : nullptr, &st),
+          "frtx_render_pixels", ctx);
+    return st;
+}
+
+// The active share of the frame below which an adaptive pass goes through frtx_render_pixels: the
+// full render's time over the sparse kernel's for the same pixels and samples, rounded down to one
+// decimal (1080p, 64 spp, one MI355X: profiles/adaptive/switch.json).  The binding's ADAPTIVE_SWITCH.
+constexpr double kAdaptiveSwitch = 0.5;
+// The first pass of an adaptive run when the caller names none (first_spp = 0): the smallest power
+// of two at which the run's sum of mean V stays inside the calibration window of the sum of the
+// actual squared error (profiles/adaptive/calibration.json).  The binding's ADAPTIVE_FIRST_SPP.
+constexpr int kAdaptiveFirstSpp = 128;
 
 // Progressive render of the whole-frame request `p` (path or ao; spp and sample_offset are the
 // driver's) on `gpus` until e <= target or the next pass would exceed max_spp.  Pass 0 renders
@@ -387,9 +417,24 @@ struct until_result {
 // each stays a prefix net); film and V from replicate_variance, spp_used counts all four, and the
 // ERROR integrator is not called.  on_pass(total spp, e, kernel ms of the pass) after every pass.
 // The loop of the Python binding's Context.render_until, film for film.
-inline until_result render_until(device_set &gpus, frt_render_params p, double target, long max_spp, int first_spp = 16,
-                                 const std::function<void(long, double, double)> &on_pass = nullptr)
+//
+// adaptive: after every pass tau = target x the film's mean (its values added one after the other
+// in double), and a pixel is active while the mean of its three V exceeds tau^2.  A later pass
+// gives every active pixel as many samples as it has (n for the most-sampled one), from the first
+// sample index not yet handed out: through frtx_render_pixels on the first context when their share
+// of the frame is below switch_share, else through the full render of n samples, after which
+// every pixel holds the new samples.  Per pixel the
+// film merges as frt_film_accumulate and V as combine_variance with that pixel's own count.  The
+// loop ends when no pixel is active (then e <= target) or when the next pass would take an active
+// pixel past max_spp.  Stopping a pixel on its own V biases it a little.
+// FRT_FLAG_SOBOL is refused.  The binding's render_until(adaptive=True), film for film.
+inline until_result render_until_adaptive(device_set &gpus, frt_render_params p, double target, long max_spp, int first_spp,
+                                          double switch_share, const std::function<void(long, double, double)> &on_pass);
+inline until_result render_until(device_set &gpus, frt_render_params p, double target, long max_spp, int first_spp = 0,
+                                 const std::function<void(long, double, double)> &on_pass = nullptr, bool adaptive = false,
+                                 double switch_share = kAdaptiveSwitch)
 {
+    if (first_spp == 0) first_spp = adaptive ? kAdaptiveFirstSpp : 16;
     if (first_spp < 2 || (first_spp & (first_spp - 1))) throw error(FRT_E_INVALID, "render_until: first_spp must be a power of two >= 2");
     if (p.integrator != FRT_INTEGRATOR_PATH && p.integrator != FRT_INTEGRATOR_AO)
         throw error(FRT_E_INVALID, "render_until: path and ao renders only (pssmlt has no error estimate, denoise is a filter)");
@@ -400,6 +445,12 @@ inline until_result render_until(device_set &gpus, frt_render_params p, double t
     p.shard_index = 0; p.shard_count = 1;
     const int64_t slots = frt_shard_slot_count(&p);
     if (slots < 0) throw error(FRT_E_INVALID, "render_until: bad render params");
+    if (adaptive) {
+        if (sobol)
+            throw error(FRT_E_INVALID, "render_until: adaptive with FRT_FLAG_SOBOL is refused -- V is an upper estimate under "
+                                       "Sobol' points and the replicates give no per-pixel error; render without the flag");
+        return render_until_adaptive(gpus, p, target, max_spp, first_spp, switch_share, on_pass);
+    }
     const size_t n3 = (size_t)p.nx * p.ny * 3;
     std::vector<float> films[4], pass(n3), vp(n3);
     until_result R;
@@ -438,6 +489,94 @@ inline until_result render_until(device_set &gpus, frt_render_params p, double t
         if (R.converged || 2 * R.spp_used > max_spp) break;
     }
     if (!sobol) R.film = films[0];
+    return R;
+}
+
+inline until_result render_until_adaptive(device_set &gpus, frt_render_params p, double target, long max_spp, int first_spp,
+                                          double switch_share, const std::function<void(long, double, double)> &on_pass)
+{
+    const int64_t slots = frt_shard_slot_count(&p);
+    const size_t npx = (size_t)p.nx * p.ny, n3 = npx * 3;
+    until_result R;
+    std::vector<float> pass(n3), vp(n3), rgb, var;
+    std::vector<int64_t> counts(npx, first_spp);
+    bool halve = false;
+    auto full_pass = [&](long n, long offset) -> double {   // pass, vp <- the frame's n samples from `offset` and their V
+        frt_render_params q = p;
+        q.spp = (int)n; q.sample_offset = (int)offset;
+        if (halve) q.samples_per_item = (int)(n / 2);
+        frt_stats st{};
+        check(frt_render_multi(gpus.data(), gpus.size(), &q, pass.data(), &st), "frt_render_multi", gpus.data()[0]);
+        if (st.work_items == (uint64_t)slots) {   // one chunk a pixel
+            halve = true;
+            q.samples_per_item = (int)(n / 2);
+            check(frt_render_multi(gpus.data(), gpus.size(), &q, pass.data(), &st), "frt_render_multi", gpus.data()[0]);
+        }
+        gpus.error(q, vp.data());
+        return st.kernel_ms;
+    };
+    // pixel i of the film <- its count's mean with n more samples (3 values each)
+    auto merge = [&](size_t i, const float *c3, const float *v3, long n) {
+        check(frt_film_accumulate(&R.film[3 * i], counts[i], c3, n, 3), "frt_film_accumulate");
+        combine_variance(&R.variance[3 * i], (long)counts[i], v3, n, 3);
+        counts[i] += n;
+    };
+    double ms = full_pass(first_spp, 0);
+    R.film = pass;
+    R.variance = vp;
+    long offset = first_spp;   // samples [0, offset) of a pixel's stream are handed out
+    long sampled = (long)npx;
+    bool sparse = false;
+    std::vector<int32_t> active;
+    for (;;) {
+        double sf = 0.0;
+        for (size_t i = 0; i < n3; ++i) sf += (double)R.film[i];
+        const double tau = target * (sf / (double)n3);
+        const double tau2 = tau * tau;
+        active.clear();
+        int64_t cmax = 0;
+        long long total = 0;
+        for (size_t i = 0; i < npx; ++i) {
+            const double m = (((double)R.variance[3 * i] + (double)R.variance[3 * i + 1]) + (double)R.variance[3 * i + 2]) / 3.0;
+            if (m > tau2) { active.push_back((int32_t)i); cmax = std::max(cmax, counts[i]); }
+            total += counts[i];
+        }
+        R.e = frame_error(R.film.data(), R.variance.data(), n3);
+        R.passes.push_back(until_pass{total, R.e, ms, sampled, sparse});
+        R.spp_used = (long)*std::max_element(counts.begin(), counts.end());
+        if (on_pass) on_pass(R.spp_used, R.e, ms);
+        R.converged = active.empty();
+        const long n = (long)cmax;   // the pass to come doubles the active pixels
+        if (R.converged || 2 * n > max_spp) break;
+        sparse = (double)active.size() < switch_share * (double)npx;
+        if (sparse) {
+            // one call per count among the active pixels (ascending), each doubling its group: after
+            // sparse passes alone that is one call with sample_offset = spp = n
+            std::vector<int64_t> before, cs;
+            for (int32_t i : active) before.push_back(counts[(size_t)i]);
+            cs = before;
+            std::sort(cs.begin(), cs.end());
+            cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+            ms = 0.0;
+            std::vector<int32_t> group;
+            for (int64_t c : cs) {
+                group.clear();
+                for (size_t k = 0; k < active.size(); ++k)
+                    if (before[k] == c) group.push_back(active[k]);
+                frt_render_params q = p;
+                q.spp = (int)c; q.sample_offset = (int)offset; q.samples_per_item = 0;
+                ms += render_pixels(gpus.data()[0], q, group, rgb, &var).kernel_ms;
+                for (size_t k = 0; k < group.size(); ++k) merge((size_t)group[k], &rgb[3 * k], &var[3 * k], (long)c);
+            }
+            sampled = (long)active.size();
+        } else {
+            ms = full_pass(n, offset);
+            for (size_t i = 0; i < npx; ++i) merge(i, &pass[3 * i], &vp[3 * i], n);
+            sampled = (long)npx;
+        }
+        offset += n;
+    }
+    R.counts.assign(counts.begin(), counts.end());
     return R;
 }
 
