@@ -195,6 +195,17 @@ class ShadowTreeInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ExitTreeInfo(ctypes.Structure):
+    """frt_exit_tree_info: what the exit-tree pass took, and what it saves."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("why", "classes", "taken", "budget_refused", "nodes_off", "n_nodes",
+                                              "nodes_added", "depth_off", "depth_on", "n_rays", "n_ext", "reserved")] + [
+        (n, ctypes.c_int64) for n in ("lds_bytes", "lds_bytes_oct", "lds_cap", "lds_cap_oct")] + [
+        (n, ctypes.c_double * 2) for n in ("v_all", "t_all", "j_all", "v_ext", "t_ext")]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if t is ctypes.c_double * 2 else getattr(self, k)) for k, t in self._fields_}
+
+
 class PlanQuery(ctypes.Structure):
     """frt_plan_query: the scene properties and the call whose launch plan selftest_plan asks for."""
     _fields_ = [(n, ctypes.c_int32) for n in ("kind", "integrator", "flags", "world_kind", "stack_needed", "has_bvh4",
@@ -232,7 +243,8 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
            "frt_selftest_path_host_env")
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
 EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
-             "frtx_selftest_plan", "frtx_selftest_shadow_tree", "frtx_render_pixels", "frtx_render_pixels_device")
+             "frtx_selftest_plan", "frtx_selftest_shadow_tree", "frtx_render_pixels", "frtx_render_pixels_device",
+             "frtx_selftest_exit_tree")
 
 
 def lib():
@@ -304,6 +316,9 @@ def lib():
     L.frtx_selftest_tree_refine.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(TreeCost), vp, vp, ctypes.c_int32]
     L.frtx_selftest_shadow_tree.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(ShadowTreeInfo), vp, vp,
                                             ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32]
+    if hasattr(L, "frtx_selftest_exit_tree"):   # (FRT_LIB_PATH may name an earlier revision's build for a timing A/B)
+        L.frtx_selftest_exit_tree.argtypes = [ctypes.POINTER(SceneView), ctypes.c_int32, ctypes.POINTER(ExitTreeInfo), vp,
+                                              vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32]
     L.frtx_selftest_trace_host.argtypes = [ctypes.POINTER(SceneView), vp, ctypes.c_int64, vp]
     L.frtx_selftest_chunk_variance.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp]
     L.frtx_render_pixels.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, ctypes.POINTER(Stats)]
@@ -895,6 +910,32 @@ def selftest_shadow_tree(scene, segments=0, seed=1):
     _check(lib().frtx_selftest_shadow_tree(ctypes.byref(view), ctypes.byref(out), dropped.ctypes.data, nodes.ctypes.data,
                                            cap, int(segments), int(seed)), "frtx_selftest_shadow_tree")
     return out.as_dict(), dropped[:int(view.n_tris)].copy(), nodes[:out.n_nodes].copy()
+
+
+EXIT_WHY = ("ran", "off", "material", "not_resident", "too_large", "nothing", "budget")
+
+
+def selftest_exit_tree(scene, mode=1):
+    """The counting hook of the exit-tree pass: (info dict, roots, taken, nodes_off, nodes_on) -- the
+    frt_exit_tree_info fields (`why_name`, and `view_of`: device triangle -> scene-view triangle, added),
+    per scene-view triangle the node its extension rays start at (0 = the main root), one row (sub, root, members, dropped, added, shared) per drop set
+    taken, and the flattened node records without the pass and with it (mode: -1 as FRT_EXIT_TREE
+    says, 0 off, 1 on)."""
+    view = scene.view()
+    cap = max(4 * int(view.n_nodes), 1) + 16
+    nodes = np.zeros((2, cap, 16), np.float32)
+    roots = np.zeros(max(int(view.n_tris), 1), np.int32)
+    taken = np.zeros((64, 6), np.int32)
+    view_of = np.zeros(max(int(view.n_tris), 1), np.int32)
+    out = ExitTreeInfo()
+    _check(lib().frtx_selftest_exit_tree(ctypes.byref(view), int(mode), ctypes.byref(out), roots.ctypes.data,
+                                         view_of.ctypes.data, taken.ctypes.data, len(taken), nodes[0].ctypes.data, nodes[1].ctypes.data, cap),
+           "frtx_selftest_exit_tree")
+    info = out.as_dict()
+    info["why_name"] = EXIT_WHY[out.why]
+    info["view_of"] = view_of[:int(view.n_tris)].copy()
+    return (info, roots[:int(view.n_tris)].copy(), taken[:min(out.taken, len(taken))].copy(),
+            nodes[0, :out.nodes_off].copy(), nodes[1, :out.n_nodes].copy())
 
 
 def selftest_trace_host(scene, rays):

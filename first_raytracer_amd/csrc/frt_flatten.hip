@@ -5,7 +5,8 @@
 // HIP runtime call; built with the kernel units' compiler and flags so that
 // its floating-point results do not depend on which unit holds it.  Also the
 // shadow-tree pass (shadow_tree): the occluder tree of area-light shadow rays
-// appended behind the main nodes.
+// appended behind the main nodes, and the exit-tree pass (exit_tree): the
+// trees extension rays start at, behind those.
 #include "frt_flatten.hpp"
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include <functional>
 
 #include "frt_kernels.hpp"   // the LDS budgets (kLdsSceneBytes, kLdsOctBytes, kLdsMaxDepth, oct_lds_node_slots)
+#include "host/exit_tree.hpp"
 #include "host/shadow_tree.hpp"
 #include "host/tree_refine.hpp"
 
@@ -393,19 +395,26 @@ static void topology_of(const std::vector<float4> &nodes, frt_refine::Topology &
 
 // the rays of one replayed frame against the leaves
 // occl (optional): per ray of R, 1 = an area-light shadow ray (light_shadow_ray)
+// from (optional): per ray of R, the device triangle an extension ray leaves (the closest hit before
+// it), -1 for a camera ray, a shadow ray and a ray that leaves a sphere.  Every ray is traced from
+// the main root here, whatever exit roots F holds: the sample is the same with the pass on and off.
 static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leaves, int frame, uint32_t seed,
-                        frt_refine::RaySet &R, std::vector<uint8_t> *occl = nullptr, std::vector<float> *origins = nullptr)
+                        frt_refine::RaySet &R, std::vector<uint8_t> *occl = nullptr, std::vector<float> *origins = nullptr,
+                        std::vector<int> *from = nullptr)
 {
     const DevScene S = host_scene(F);
-    struct Ray { f3 o, d; float tmax; bool shadow, occl; };
+    struct Ray { f3 o, d; float tmax; bool shadow, occl; int from; };
     std::vector<Ray> rays;
     std::vector<int> stack(std::max(F.depth + 1, 1));
     for (int pix = 0; pix < frame * frame; ++pix) {
         PathState<float> P;
         path_begin<kMatsAll>(P, S, pix % frame, pix / frame, frame, frame, seed, (uint32_t)pix, 0u);
+        int last = -1;   // the primitive the path stands on
         for (;;) {
-            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow, light_shadow_ray(P)});
+            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow, light_shadow_ray(P),
+                               (P.shadow || last < 0 || (last & FRT_PRIM_SPHERE)) ? -1 : last});
             const Hit<float> h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), light_shadow_ray(P));
+            if (!P.shadow) last = h.prim;
             uint32_t n_ext = 0, n_sh = 0;
             if (path_shade<kMatsAll>(P, S, h, kRefineMaxDepth, n_ext, n_sh)) break;
         }
@@ -425,6 +434,7 @@ static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leave
     R.n_prims = (int)R.prim_ref.size();
     R.tmin.resize(n); R.tmax.resize(n); R.anyhit.resize(n); R.live.resize(n);
     if (occl) occl->assign(n, 0);
+    if (from) from->assign(n, -1);
     if (origins) origins->clear();
     R.slab.resize((size_t)nl * n * 6);
     R.prim_t.resize((size_t)n * R.n_prims);
@@ -441,6 +451,7 @@ static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leave
         R.tmax[i] = q.tmax;
         R.anyhit[i] = q.shadow ? 1 : 0;
         if (occl) (*occl)[i] = q.occl ? 1 : 0;
+        if (from) (*from)[i] = q.from;
         if (origins && q.occl) { origins->push_back(q.o.x); origins->push_back(q.o.y); origins->push_back(q.o.z); }
         const float inv[3] = {T.sr.invd.x, T.sr.invd.y, T.sr.invd.z}, oi[3] = {T.sr.oinv.x, T.sr.oinv.y, T.sr.oinv.z};
         for (int l = 0; l < nl; ++l) {
@@ -551,6 +562,40 @@ static bool shadow_tree_knob()
     return !(e && std::atoi(e) == 0);
 }
 
+// sv's triangles in device order (tri_view) for the proofs of the shadow-tree and exit-tree passes,
+// which name triangles as the leaves do
+struct ProofGeometry {
+    std::vector<double> tv, tn;
+    std::vector<uint8_t> smooth;
+    frt_shadow::Geometry g;
+};
+static void proof_geometry(const frt_scene_view *sv, const FlatScene &F, ProofGeometry &pg)
+{
+    const int nt = sv->n_tris;
+    pg.tv.resize(9 * (size_t)nt);
+    pg.smooth.assign(nt, 0);
+    bool any_smooth = false;
+    for (int d = 0; d < nt; ++d) {
+        const int i = F.tri_view[d];
+        std::copy(&sv->tri_v[9 * (size_t)i], &sv->tri_v[9 * (size_t)i] + 9, &pg.tv[9 * (size_t)d]);
+        pg.smooth[d] = sv->tri_geometry_normal && !sv->tri_geometry_normal[i];
+        any_smooth |= pg.smooth[d] != 0;
+    }
+    if (any_smooth) {
+        pg.tn.resize(9 * (size_t)nt);
+        for (int d = 0; d < nt; ++d)
+            std::copy(&sv->tri_n[9 * (size_t)F.tri_view[d]], &sv->tri_n[9 * (size_t)F.tri_view[d]] + 9, &pg.tn[9 * (size_t)d]);
+    }
+    frt_shadow::Geometry &g = pg.g;
+    g.n_tris = nt; g.n_spheres = sv->n_spheres;
+    g.tri_v = pg.tv.data(); g.tri_n = any_smooth ? pg.tn.data() : nullptr; g.tri_smooth = pg.smooth.data();
+    g.sphere = sv->sphere;
+    g.lights = F.lights.data(); g.n_lights = (int)F.lights.size(); g.sphere_bit = FRT_PRIM_SPHERE;
+    for (int k = 0; k < 3; ++k) { g.cam_o[k] = sv->cam_origin[k]; g.cam_u[k] = sv->cam_u[k]; g.cam_v[k] = sv->cam_v[k]; }
+    g.lens_r = sv->cam_lens_radius;
+    g.eps = (double)Cst<float>::eps;
+}
+
 // sv's triangles in device order (tri_view) for the proof, which names triangles as the leaves do
 static void shadow_tree(const frt_scene_view *sv, FlatScene &F)
 {
@@ -566,27 +611,9 @@ static void shadow_tree(const frt_scene_view *sv, FlatScene &F)
         }
     if (!tree_in_lds(F) || F.nodes.empty()) { I.why = FlatScene::kShadowNotResident; return; }
     const int nt = sv->n_tris;
-    std::vector<double> tv(9 * (size_t)nt), tn;
-    std::vector<uint8_t> smooth(nt, 0);
-    bool any_smooth = false;
-    for (int d = 0; d < nt; ++d) {
-        const int i = F.tri_view[d];
-        std::copy(&sv->tri_v[9 * (size_t)i], &sv->tri_v[9 * (size_t)i] + 9, &tv[9 * (size_t)d]);
-        smooth[d] = sv->tri_geometry_normal && !sv->tri_geometry_normal[i];
-        any_smooth |= smooth[d] != 0;
-    }
-    if (any_smooth) {
-        tn.resize(9 * (size_t)nt);
-        for (int d = 0; d < nt; ++d) std::copy(&sv->tri_n[9 * (size_t)F.tri_view[d]], &sv->tri_n[9 * (size_t)F.tri_view[d]] + 9, &tn[9 * (size_t)d]);
-    }
-    frt_shadow::Geometry g;
-    g.n_tris = nt; g.n_spheres = sv->n_spheres;
-    g.tri_v = tv.data(); g.tri_n = any_smooth ? tn.data() : nullptr; g.tri_smooth = smooth.data();
-    g.sphere = sv->sphere;
-    g.lights = F.lights.data(); g.n_lights = (int)F.lights.size(); g.sphere_bit = FRT_PRIM_SPHERE;
-    for (int k = 0; k < 3; ++k) { g.cam_o[k] = sv->cam_origin[k]; g.cam_u[k] = sv->cam_u[k]; g.cam_v[k] = sv->cam_v[k]; }
-    g.lens_r = sv->cam_lens_radius;
-    g.eps = (double)Cst<float>::eps;
+    ProofGeometry pg;
+    proof_geometry(sv, F, pg);
+    const frt_shadow::Geometry &g = pg.g;
     frt_shadow::Classified c;
     frt_shadow::classify(g, c);
     if (c.why != frt_shadow::kRan) {
@@ -725,7 +752,194 @@ void shadow_origins_host(const FlatScene &F, std::vector<float> &origins)
     sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl, &origins);
 }
 
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine, int shadow)
+// ---- the trees extension rays start at (DESIGN.md "Exit trees") ----
+// An extension ray of a lambertian vertex leaves its triangle on the stored normal's side and
+// climbs from there; its origin lies inside the box of the leaf it leaves and of every ancestor, so
+// from the main root the first leaf it reaches is its own, two triangles in the plane it has just
+// left.  host/exit_tree.cpp proves per origin triangle which triangles such a ray cannot report a
+// hit on; per main-tree leaf the largest subtree made of those alone is its drop set (a wall: its
+// own leaf; a face of a box: the box's subtree where the tree groups the box), and the main tree
+// without it -- frt_shadow::build's rules, the copied ancestors appended behind the main and shadow
+// nodes -- is where trav_begin starts those rays.  The root's node index goes into the third word of
+// the triangle's second shading record (0 = the main root).  Closest hits are unchanged, so films
+// and ray counts are; only visits and triangle tests drop.  Among the distinct drop sets the pass
+// takes, greedily, those with the largest fall of J = V + kRefineW T on the refinement pass's
+// fitting replay per appended node, while the appended nodes leave the scene on the LDS plan it has.
+static bool exit_tree_knob()
+{
+    const char *e = std::getenv("FRT_EXIT_TREE");
+    return !(e && std::atoi(e) == 0);
+}
+
+// Blocks of the LDS plans that a CU holds: a block's LDS -- the traversal stack and the item state
+// of its 256 lanes, then the scene -- is allocated in granules of 1280 B out of 160 KiB.  Measured
+// on the Cornell octant plan (8-entry stack: 18432 B before the scene), profiles/exittree/
+// exit_cap.jsonl: a scene of 13328 B (31760 B a block, 25 granules, 5 blocks) runs the path kernel
+// in 186.6 ms and AO in 25.0 ms, one of 13712 B (32144 B, 26 granules, 4 blocks) in 209.3 ms and
+// 28.3 ms -- inside kLdsOctBytes, which the residency rule keeps.  The exit trees are worth less
+// than a block, so their nodes must leave this count where it is.
+constexpr size_t kLdsGranule = 1280, kLdsCuBytes = 160 * 1024;
+static int lds_blocks_per_cu(const FlatScene &F, size_t scene_bytes)
+{
+    const size_t stack = F.depth < 8 ? 8 : 16;   // the LDS plans' stack classes (frt_plans.hpp)
+    const size_t block = (stack + kItemWords) * kBlock * sizeof(int) + scene_bytes;
+    return (int)(kLdsCuBytes / ((block + kLdsGranule - 1) / kLdsGranule * kLdsGranule));
+}
+constexpr int kExitMaxRoot = 1 << 10;   // node indices the kernels carry above PathState::depth (kExitShift)
+
+static void exit_tree(const frt_scene_view *sv, FlatScene &F)
+{
+    auto &I = F.exit;
+    DevScene &S = F.meta;
+    I.nodes_before = (int)(F.nodes.size() / 4);
+    I.root.assign((size_t)std::max(sv->n_tris, 0), 0);
+    // dielectric and the specular lobes leave from p - eps n: only lambertian / diffuse_light scenes
+    for (int i = 0; i < sv->n_materials; ++i)
+        if (sv->materials[i].type != FRT_MAT_LAMBERTIAN && sv->materials[i].type != FRT_MAT_DIFFUSE_LIGHT) {
+            I.why = FlatScene::kExitMaterial;
+            return;
+        }
+    if (!tree_in_lds(F) || F.nodes.empty() || S.root != 0) { I.why = FlatScene::kExitNotResident; return; }
+    ProofGeometry pg;
+    proof_geometry(sv, F, pg);
+    frt_exit::Hidden hid;
+    frt_exit::classify(pg.g, hid);
+    if (hid.why != frt_exit::kRan) { I.why = FlatScene::kExitTooLarge; return; }
+    std::vector<float> nodes(4 * F.nodes.size());
+    memcpy(nodes.data(), F.nodes.data(), sizeof(float4) * F.nodes.size());
+    std::vector<frt_exit::Class> cls;
+    frt_exit::classes(nodes, S.root, FRT_PRIM_SPHERE, kLeafCountShift, hid, cls);
+    I.classes = (int)cls.size();
+    if (cls.empty()) { I.why = FlatScene::kExitNothing; return; }
+
+    // the fitting replay against the leaves, with the triangle every extension ray leaves
+    frt_refine::Topology t0;
+    std::vector<RefineLeaf> leaves;
+    std::vector<int> leaf_refs;
+    topology_all(F.nodes, t0, leaves, leaf_refs);
+    frt_refine::RaySet R;
+    std::vector<int> from;
+    sample_rays(F, leaves, kRefineFitFrame, kRefineFitSeed, R, nullptr, nullptr, &from);
+    const std::vector<uint8_t> live0 = R.live;
+
+    // each class alone: its tree on a copy of the nodes, the nodes it appends and the fall of J
+    struct Cand { int cls, added; double gain; };
+    std::vector<Cand> cand;
+    auto as_float4 = [](const std::vector<float> &v) {
+        std::vector<float4> o(v.size() / 4);
+        memcpy(o.data(), v.data(), sizeof(float) * v.size());
+        return o;
+    };
+    for (int c = 0; c < (int)cls.size(); ++c) {
+        std::vector<float> trial = nodes;
+        frt_shadow::Tree t;
+        frt_shadow::build(trial, S.root, cls[c].dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
+        if (t.empty || t.root <= 0 || t.root >= kExitMaxRoot || t.dropped_leaves == 0) continue;
+        frt_refine::Topology tt;
+        std::vector<RefineLeaf> l2;
+        std::vector<int> r2;
+        topology_all(as_float4(trial), tt, l2, r2);
+        if (r2 != leaf_refs) continue;   // (appended nodes name the main tree's leaves only)
+        bool any = false;
+        for (int i = 0; i < R.n; ++i) {
+            const bool mine = from[i] >= 0 && std::binary_search(cls[c].members.begin(), cls[c].members.end(), from[i]);
+            R.live[i] = live0[i] && mine;
+            any |= R.live[i] != 0;
+        }
+        if (!any) continue;
+        R.root.clear();
+        const double j0 = frt_refine::cost_j(frt_refine::tree_cost(tt, R), kRefineW);
+        R.root.assign(R.n, tt.n_leaves + t.root);
+        const double j1 = frt_refine::cost_j(frt_refine::tree_cost(tt, R), kRefineW);
+        if (j1 < j0) cand.push_back(Cand{c, t.added, j0 - j1});
+    }
+    if (cand.empty()) { I.why = FlatScene::kExitNothing; return; }
+    // by gain per appended node (a tree that appends nothing first), then gain, then class order
+    std::stable_sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) {
+        if ((a.added == 0) != (b.added == 0)) return a.added == 0;
+        const double ra = a.gain / std::max(a.added, 1), rb = b.gain / std::max(b.added, 1);
+        if (ra != rb) return ra > rb;
+        return a.gain > b.gain;
+    });
+    // the appended nodes must leave the scene on the plan it has (pick_launcher_t reads these sizes)
+    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
+    const int nn0 = I.nodes_before;
+    const bool lds0 = sizeof(float4) * (4 * (size_t)nn0 + rest) <= kLdsSceneBytes;
+    const bool oct0 = !F.nodes_oct.empty();
+    auto planar = [&](int nn) { return sizeof(float4) * (4 * (size_t)nn + rest); };
+    auto octant = [&](int nn) { return sizeof(float4) * (oct_lds_node_slots(nn) + rest); };
+    auto fits = [&](int nn1) {
+        const bool lds1 = planar(nn1) <= kLdsSceneBytes;
+        const bool oct1 = octant(nn1) <= kLdsOctBytes;
+        if (lds0 != lds1 || oct0 != oct1) return false;
+        // ... and with as many blocks on a CU (lds_blocks_per_cu)
+        if (lds0 && lds_blocks_per_cu(F, planar(nn1)) != lds_blocks_per_cu(F, planar(nn0))) return false;
+        return !oct0 || lds_blocks_per_cu(F, octant(nn1)) == lds_blocks_per_cu(F, octant(nn0));
+    };
+    bool refused = false;
+    for (const Cand &k : cand) {
+        const frt_exit::Class &c = cls[k.cls];
+        std::vector<float> next = nodes;
+        frt_shadow::Tree t;
+        frt_shadow::build(next, S.root, c.dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
+        if (!fits((int)(next.size() / 16)) || t.root >= kExitMaxRoot) { refused = true; continue; }
+        nodes.swap(next);
+        for (int d : c.members) I.root[d] = t.root;
+        I.taken.push_back({c.sub, t.root, (int)c.members.size(), c.n_dropped, t.added, t.shared, k.gain});
+        I.added += t.added;
+    }
+    if (I.taken.empty()) { I.why = refused ? FlatScene::kExitBudget : FlatScene::kExitNothing; return; }
+    I.budget_refused = refused;
+    F.nodes.resize(nodes.size() / 4);
+    memcpy(F.nodes.data(), nodes.data(), sizeof(float) * nodes.size());
+    if (oct0) F.nodes_oct.resize(8 * F.nodes.size());
+    for (size_t d = 0; d < I.root.size(); ++d)
+        if (I.root[d]) F.tshade[2 * d + 1].z = i2f(I.root[d]);
+    I.why = FlatScene::kExitRan;
+}
+
+bool exit_cost_host(const FlatScene &F, ExitCost &out)
+{
+    out = ExitCost{};
+    if (!tree_in_lds(F) || F.nodes.empty()) return false;
+    frt_refine::Topology t;
+    std::vector<RefineLeaf> leaves;
+    std::vector<int> leaf_refs;
+    topology_all(F.nodes, t, leaves, leaf_refs);
+    frt_refine::RaySet R;
+    std::vector<uint8_t> occl;
+    std::vector<int> from;
+    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl, nullptr, &from);
+    const DevScene S = host_scene(F);
+    auto slot = [&](int ref) {
+        return ref >= 0 ? t.n_leaves + ref : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), ref) - leaf_refs.begin());
+    };
+    const std::vector<uint8_t> live0 = R.live;
+    out.n_rays = R.n;
+    for (int i = 0; i < R.n; ++i) out.n_ext += from[i] >= 0;
+    for (int on = 0; on < 2; ++on) {
+        // every ray where the kernels start it: area-light shadow rays at the shadow root (trav_begin
+        // tests no box there; an empty shadow tree ends them at once), extension rays at their exit root
+        R.root.assign(R.n, t.root);
+        R.live = live0;
+        for (int i = 0; i < R.n; ++i) {
+            if (occl[i] && S.sroot != S.root) {
+                if (S.sroot == kSentinel) R.live[i] = 0;
+                else { R.root[i] = slot(S.sroot); R.live[i] = 1; }
+            } else if (on && from[i] >= 0 && from[i] < (int)F.exit.root.size() && F.exit.root[from[i]]) {
+                R.root[i] = slot(F.exit.root[from[i]]);
+            }
+        }
+        const frt_refine::Cost all = frt_refine::tree_cost(t, R);
+        out.V_all[on] = all.V; out.T_all[on] = all.T; out.J_all[on] = frt_refine::cost_j(all, kRefineW);
+        for (int i = 0; i < R.n; ++i) R.live[i] = R.live[i] && from[i] >= 0;
+        const frt_refine::Cost ext = frt_refine::tree_cost(t, R);
+        if (out.n_ext > 0) { out.V_ext[on] = ext.V * R.n / out.n_ext; out.T_ext[on] = ext.T * R.n / out.n_ext; }
+    }
+    return true;
+}
+
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine, int shadow, int exit)
 {
     auto fail = [&](int code, const std::string &m) { err = m; return code; };
     const int nt = sv->n_tris, ns = sv->n_spheres, nm = sv->n_materials;
@@ -1030,6 +1244,11 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     if (shadow < 0 ? shadow_tree_knob() : shadow != 0) {
         shadow_tree(sv, F);
         again |= F.shadow.why == FlatScene::kShadowRan;
+    }
+    // the exit trees over the same tree: their nodes go behind the shadow tree's
+    if (exit < 0 ? exit_tree_knob() : exit != 0) {
+        exit_tree(sv, F);
+        again |= F.exit.why == FlatScene::kExitRan;
     }
     if (again) derive_trees();
     S.n_nodes = (int)(F.nodes.size() / 4);

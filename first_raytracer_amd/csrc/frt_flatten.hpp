@@ -34,13 +34,35 @@ struct FlatScene {
         int n_dropped = 0, rule_a = 0, rule_b = 0, nodes_main = 0, added = 0, shared = 0;
         bool empty = false;
     } shadow;
+    // what the exit-tree pass did (frt_flatten.hip exit_tree): why != kExitRan leaves `nodes` and the
+    // shading records untouched (every exit root 0 = the main root)
+    enum { kExitRan = 0, kExitOff, kExitMaterial, kExitNotResident, kExitTooLarge, kExitNothing, kExitBudget };
+    struct ExitClass { int sub, root, members, dropped, added, shared; double gain; };   // sub: the dropped subtree (node, or ~leaf)
+    struct {
+        int why = kExitOff;
+        int classes = 0;                // distinct drop sets found
+        std::vector<ExitClass> taken;   // those given a tree, in the order taken
+        std::vector<int> root;          // per device triangle: the node its extension rays start at, 0 = the main root
+        int nodes_before = 0, added = 0;
+        bool budget_refused = false;    // a drop set with a gain was left out for the LDS budget
+    } exit;
 };
 
 // f64: also build the fp64 records of the fp64 kernels (DESIGN.md "Precision")
 // refine: the topology refinement of LDS-resident binary trees; -1 = as FRT_TREE_REFINE says
 // (default on, read at each call), 0 = off, 1 = on
 // shadow: the occluder tree of area-light shadow rays behind the main nodes, the same way (FRT_SHADOW_TREE)
-int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1, int shadow = -1);
+// exit: the trees extension rays start at, behind those, the same way (FRT_EXIT_TREE)
+int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1, int shadow = -1,
+                  int exit = -1);
+// V, T and J of the refinement pass's validation rays, each started where the kernels start it, with
+// the exit roots ignored (index 0) and used (1): over all rays, and V and T over the extension rays
+// alone (per extension ray); false when the tree is not LDS-resident
+struct ExitCost {
+    double V_all[2] = {0, 0}, T_all[2] = {0, 0}, J_all[2] = {0, 0}, V_ext[2] = {0, 0}, T_ext[2] = {0, 0};
+    int n_rays = 0, n_ext = 0;
+};
+bool exit_cost_host(const FlatScene &F, ExitCost &out);
 // V and T of the refinement pass's validation rays that are area-light shadow rays, started at the
 // main root (index 0) and at the shadow root (1); stops: how many of them miss that root's box
 struct ShadowCost { double V[2] = {0, 0}, T[2] = {0, 0}; int n_rays = 0, stops[2] = {0, 0}; };

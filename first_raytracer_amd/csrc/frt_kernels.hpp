@@ -217,6 +217,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
         else return P.rtmax;
     };
 
+    // The lambertian path kernels of the LDS plans start an extension ray at its vertex's exit
+    // root (host/exit_tree.cpp; the pass covers LDS-resident binary trees only).  Camera rays
+    // (depth word 0) and shadow rays of either kind start where they did.
+    constexpr bool kExit = LDS_SCENE && KIND == FRT_INTEGRATOR_PATH && (MATS & kMatsSpecAny) == 0 &&
+                           (WORLD == FRT_WORLD_BVH || WORLD == kWorldBvh2Oct);
+
     unsigned long long diag_t0 = FRT_DIAG_CLOCK();
     for (;;) {
         FRT_DIAG_TICK(6);
@@ -235,7 +241,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
                     if (path_after_shadow<MATS>(P, T.h.prim < 0)) {
                         if constexpr (kLean) flush_L();
                         shadow_done = true;
-                        tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, ray_tmax());
+                        if constexpr (kExit) {
+                            const int xr = exit_root(P);
+                            tracing = trav_begin(T, S, xr ? xr : S.root, P.ro, P.rd, ray_tmax());
+                        } else {
+                            tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, ray_tmax());
+                        }
                         pending = !tracing;
                     } else {                                      // path ended (P.term): shade finishes it
                         tracing = false;
@@ -259,7 +270,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
             pending = false;
             if constexpr (kLean)
                 P.key = smp_key<MATS>(W.seed, (uint32_t)I.get(kIsPix), (uint32_t)(I.get(kIsCur) - 1) + W.s_off);
-            const bool done = shade_kind<KIND, MATS>(P, S, T.h, W.max_depth, ne, ns);
+            const bool done = shade_kind<KIND, MATS, kExit>(P, S, T.h, W.max_depth, ne, ns);
             if (done || kLean) flush_L();   // fp32 chunk sums in either precision
             active = !done;
             next_ray = !done;
@@ -347,7 +358,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
             // an area-light shadow ray starts at the shadow root (the environment-NEE ray has t_max = tmax)
             const R tm = ray_tmax();
             const bool occl = KIND == FRT_INTEGRATOR_PATH && P.shadow && ((MATS & kMatsEnvNee) == 0 || tm < R(1));
-            tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, tm, occl);
+            if constexpr (kExit) {
+                const int xr = P.shadow ? 0 : exit_root(P);
+                tracing = trav_begin(T, S, xr ? xr : S.root, P.ro, P.rd, tm, occl);
+            } else {
+                tracing = trav_begin_world<WORLD>(T, S, P.ro, P.rd, tm, occl);
+            }
             pending = !tracing;
         }
         diag_t0 = FRT_DIAG_CLOCK();

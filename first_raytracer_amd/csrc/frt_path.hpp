@@ -305,6 +305,9 @@ template <typename R> FRT_HD R bvh_tmin(V3<R> o)
 // interval), a per-lane choice between two boxes held in SGPRs cost the Cornell
 // kernel 3.4 % (profiles/shadowtree), and on Cornell no shadow segment misses
 // the occluders' box anyway.
+// An extension ray of a lambertian vertex passes its exit root as `root`
+// (exit_root): the main tree without what its surface hides (host/exit_tree.cpp).
+// That tree lies inside the main root's box, so the box test stays this one.
 template <typename R>
 FRT_HD bool trav_begin(Trav<R> &T, const DevScene &S, int root, V3<R> o, V3<R> d, R tmax, bool occl = false)
 {
@@ -540,6 +543,16 @@ FRT_HD Hit<R> trace_bvh(const DevScene &S, V3<R> o, V3<R> d, R tmax, bool anyhit
     Trav<R> T;
     if (trav_begin(T, S, S.root, o, d, tmax, occl))
         while (!bvh2_step<STRIDE>(T, S, o, d, anyhit, stk)) {}
+    return T.h;
+}
+
+// ... a closest-hit extension ray from its exit root (exit_root; 0 = the main root)
+template <int STRIDE, typename R>
+FRT_HD Hit<R> trace_bvh_from(const DevScene &S, int xroot, V3<R> o, V3<R> d, R tmax, int *stk)
+{
+    Trav<R> T;
+    if (trav_begin(T, S, xroot ? xroot : S.root, o, d, tmax))
+        while (!bvh2_step<STRIDE>(T, S, o, d, false, stk)) {}
     return T.h;
 }
 
@@ -972,9 +985,23 @@ template <typename R> struct PathState {
     V3<R> prev_p;         // previous hit point (MIS distance, path.cpp:25)
     R prev_pdf;           // bsdf pdf of the previous bounce
     bool prev_spec;       // previous bounce was modified_phong / metal / dielectric: no MIS on light hits
-    int depth;
+    int depth;            // path_shade<MATS, true>: the exit root above it (path_depth / exit_root)
     RngKey key;
 };
+
+// The exit root of the vertex a path stands on -- the node an extension ray
+// from there starts at (host/exit_tree.cpp), 0 = the main root -- rides in the
+// high bits of PathState::depth, so that no register is live for it across the
+// shadow traversal: a render's depth stays below 2^17 (max_depth < 100000), a
+// node index of an LDS-resident tree below 2^10.  Only path_shade<MATS, true>
+// writes and masks it: the lambertian path kernels of the LDS plans, and the
+// host replay.
+constexpr int kExitShift = 20;
+template <typename R> FRT_HD int path_depth(const PathState<R> &P) { return P.depth & ((1 << kExitShift) - 1); }
+// the root of P's extension ray; not for its shadow ray (that one may point under the surface)
+template <typename R> FRT_HD int exit_root(const PathState<R> &P) { return P.depth >> kExitShift; }
+// the word the flattener wrote for triangle ref (third of its second shading record)
+FRT_HD int prim_exit_root(const DevScene &S, int ref) { return (ref & FRT_PRIM_SPHERE) ? 0 : f2i(shade_part(S, ref, 1).z); }
 
 // path.cpp:129-136 + camera.h:30-35 (+ util.h:21-41 thin lens)
 template <int MATS = kMatsNone, typename R>
@@ -1108,7 +1135,9 @@ FRT_HD bool mat_no_mis(int t) { return t == FRT_MAT_MODIFIED_PHONG || t == FRT_M
 // Returns true when the path is finished (P.L is the sample's radiance).
 // MATS = false compiles the lambertian / diffuse_light scenes' kernel: the
 // specular branch is dead code there (it would cost registers and code size).
-template <int MATS = kMatsAll, typename R>
+// EXIT: the vertex's exit root is kept above P.depth for the extension ray's
+// start (exit_root); the other kernels compile none of it.
+template <int MATS = kMatsAll, bool EXIT = false, typename R>
 FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
     constexpr bool kEnvNee = (MATS & kMatsEnvNee) != 0;
@@ -1119,6 +1148,7 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
         return false;
     }
     if (P.term) return true;                            // finished in the traversal loop
+    if constexpr (EXIT) P.depth = path_depth(P);        // the last vertex's root has served
     if (h.prim < 0) {                                   // path.cpp:115 environment
         if constexpr (kEnvNee) {                        // the previous vertex also sampled the image: MIS, as a light hit
             if (P.depth != 0 && !P.prev_spec) {
@@ -1275,6 +1305,8 @@ FRT_HD bool path_shade(PathState<R> &P, const DevScene &S, const Hit<R> &h, int 
         P.ro = origin; P.rd = wo; P.rtmax = Cst<R>::tmax;
         ++P.depth; ++n_ext;
     }
+    // a lambertian vertex: the extension ray leaves from p + eps n into n's cosine lobe (kExitShift)
+    if constexpr (EXIT) P.depth |= prim_exit_root(S, h.prim) << kExitShift;
     return false;
 }
 
@@ -1413,14 +1445,14 @@ FRT_HD float depth_moment_floor(float x, float y, float k)
 }
 
 // integrator dispatch of the megakernel / self-test (KIND = FRT_INTEGRATOR_*)
-template <int KIND, int MATS, typename R>
+template <int KIND, int MATS, bool EXIT = false, typename R>
 FRT_HD bool shade_kind(PathState<R> &P, const DevScene &S, const Hit<R> &h, int max_depth, uint32_t &n_ext, uint32_t &n_sh)
 {
     if constexpr (KIND == FRT_INTEGRATOR_AO) return ao_shade<MATS>(P, S, h, n_sh);
     else if constexpr (KIND == FRT_INTEGRATOR_NORMALS) return normals_shade<MATS>(P, S, h);
     else if constexpr (KIND == FRT_INTEGRATOR_ALBEDO) return albedo_shade(P, S, h);
     else if constexpr (KIND == FRT_INTEGRATOR_DEPTH) return depth_shade(P, S, h);
-    else return path_shade<MATS>(P, S, h, max_depth, n_ext, n_sh);
+    else return path_shade<MATS, EXIT>(P, S, h, max_depth, n_ext, n_sh);
 }
 
 }  // namespace frt

@@ -31,20 +31,24 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
             for (;;) {
                 Hit<R> h;
                 const bool occl = p->integrator != FRT_INTEGRATOR_AO && light_shadow_ray(P);   // starts at the shadow root
+                // an extension ray of the path integrator starts at its vertex's exit root (binary tree; 0 = the main root)
+                const int xroot = p->integrator == FRT_INTEGRATOR_PATH && !P.shadow ? exit_root(P) : 0;
                 if (S.world_kind == FRT_WORLD_LIST) {
                     h = trace<FRT_WORLD_LIST, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data());
                 } else if constexpr (!kIsF64<R>) {
                     h = wide ? trace<kWorldBvh4, 1, kSelftestStack>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data())
+                        : xroot ? trace_bvh_from<1>(S, xroot, P.ro, P.rd, P.rtmax, stack.data())
                              : trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), occl);
                 } else {
-                    h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), occl);
+                    h = xroot ? trace_bvh_from<1>(S, xroot, P.ro, P.rd, P.rtmax, stack.data())
+                              : trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), occl);
                 }
                 n_ext = n_sh = 0;
                 const bool done = p->integrator == FRT_INTEGRATOR_AO ? ao_shade<MATS>(P, S, h, n_sh)
                                   : p->integrator == FRT_INTEGRATOR_NORMALS ? normals_shade<MATS>(P, S, h)
                                   : p->integrator == FRT_INTEGRATOR_ALBEDO ? albedo_shade(P, S, h)
                                   : p->integrator == FRT_INTEGRATOR_DEPTH ? depth_shade(P, S, h)
-                                  : path_shade<MATS>(P, S, h, p->max_depth, n_ext, n_sh);
+                                  : path_shade<MATS, true>(P, S, h, p->max_depth, n_ext, n_sh);
                 cnt[1] += n_ext; cnt[2] += n_sh;
                 if (done) break;
             }
@@ -186,7 +190,7 @@ extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost
     for (int on = 0; on < 2; ++on) {
         FlatScene F;
         std::string err;
-        const int rc = flatten_scene(sv, F, err, false, on, 0);   // the main tree alone: no shadow-tree nodes behind it
+        const int rc = flatten_scene(sv, F, err, false, on, 0, 0);   // the main tree alone: no shadow-tree or exit-tree nodes behind it
         if (rc != FRT_OK) return rc;
         TreeCost c;
         const bool applies = tree_cost_host(F, c);
@@ -208,7 +212,7 @@ extern "C" int frtx_selftest_shadow_tree(const frt_scene_view *sv, frt_shadow_tr
     if (!sv || !out || segments < 0) return FRT_E_INVALID;
     FlatScene F;
     std::string err;
-    const int rc = flatten_scene(sv, F, err, false, -1, 1);
+    const int rc = flatten_scene(sv, F, err, false, -1, 1, 0);   // no exit-tree nodes behind the shadow tree's
     if (rc != FRT_OK) return rc;
     const auto &I = F.shadow;
     memset(out, 0, sizeof(*out));
@@ -253,6 +257,61 @@ extern "C" int frtx_selftest_shadow_tree(const frt_scene_view *sv, frt_shadow_tr
                 float u, v;
                 if (prim_t(S, t, o, d, bvh_tmin(o), 1.0f - Cst<float>::shadow_eps, u, v) > 0.0f) ++out->segment_hits;
             }
+        }
+    }
+    return FRT_OK;
+}
+
+// Counting hook of the exit-tree pass (frt_flatten.hip exit_tree): the scene flattened without the
+// pass and with it (mode: -1 as FRT_EXIT_TREE says, 0 off, 1 on), what the pass took, the root of
+// every triangle, and the traversal cost of the validation rays with the roots ignored and used
+extern "C" int frtx_selftest_exit_tree(const frt_scene_view *sv, int32_t mode, frt_exit_tree_info *out, int32_t *roots,
+                                       int32_t *view_of, int32_t *taken, int32_t max_taken, float *nodes_off,
+                                       float *nodes_on, int32_t max_nodes)
+{
+    if (!sv || !out || mode < -1 || mode > 1 || max_taken < 0) return FRT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    FlatScene F0, F;
+    std::string err;
+    int rc = flatten_scene(sv, F0, err, false, -1, -1, 0);
+    if (rc == FRT_OK) rc = flatten_scene(sv, F, err, false, -1, -1, mode);
+    if (rc != FRT_OK) return rc;
+    const auto &I = F.exit;
+    out->why = I.why;
+    out->classes = I.classes;
+    out->taken = (int32_t)I.taken.size();
+    out->nodes_off = (int32_t)(F0.nodes.size() / 4);
+    out->n_nodes = (int32_t)(F.nodes.size() / 4);
+    out->nodes_added = I.added;
+    out->budget_refused = I.budget_refused ? 1 : 0;
+    out->depth_off = F0.depth; out->depth_on = F.depth;
+    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
+    out->lds_bytes = (int64_t)(sizeof(float4) * (F.nodes.size() + rest));
+    out->lds_bytes_oct = F.nodes_oct.empty() ? 0 : (int64_t)(sizeof(float4) * (oct_lds_node_slots(out->n_nodes) + rest));
+    out->lds_cap = (int64_t)kLdsSceneBytes; out->lds_cap_oct = (int64_t)kLdsOctBytes;
+    if (out->nodes_off > max_nodes || out->n_nodes > max_nodes) return FRT_E_INVALID;
+    if (nodes_off) memcpy(nodes_off, F0.nodes.data(), F0.nodes.size() * sizeof(float4));
+    if (nodes_on) memcpy(nodes_on, F.nodes.data(), F.nodes.size() * sizeof(float4));
+    if (roots)
+        for (int d = 0; d < sv->n_tris; ++d) {
+            const int r = f2i(F.tshade[2 * (size_t)d + 1].z);
+            if (r != (d < (int)I.root.size() ? I.root[d] : 0)) return FRT_E_UNSUPPORTED;   // the record and the meta disagree
+            roots[F.tri_view[d]] = r;
+        }
+    if (view_of)
+        for (int d = 0; d < sv->n_tris; ++d) view_of[d] = F.tri_view[d];
+    if (taken)
+        for (int k = 0; k < out->taken && k < max_taken; ++k) {
+            const auto &c = I.taken[k];
+            const int32_t rec[6] = {c.sub, c.root, c.members, c.dropped, c.added, c.shared};
+            memcpy(taken + 6 * k, rec, sizeof(rec));
+        }
+    ExitCost c;
+    if (exit_cost_host(F, c)) {
+        out->n_rays = c.n_rays; out->n_ext = c.n_ext;
+        for (int on = 0; on < 2; ++on) {
+            out->v_all[on] = c.V_all[on]; out->t_all[on] = c.T_all[on]; out->j_all[on] = c.J_all[on];
+            out->v_ext[on] = c.V_ext[on]; out->t_ext[on] = c.T_ext[on];
         }
     }
     return FRT_OK;

@@ -614,6 +614,30 @@ typedef struct frt_shadow_tree_info {
 } frt_shadow_tree_info;
 int frtx_selftest_shadow_tree(const frt_scene_view *scene, frt_shadow_tree_info *out, uint8_t *dropped, float *nodes,
                               int32_t max_nodes, int64_t segments, uint32_t seed);
+/* The counting hook of the exit-tree pass (FRT_EXIT_TREE, README): the scene is flattened without
+ * the pass and with it as `mode` says (-1 the environment, 0 off, 1 on).  why: 0 the pass ran,
+ * 1 switched off, 2 a material other than lambertian / diffuse_light, 3 the binary tree is not
+ * LDS-resident, 4 coordinates too large for the proof, 5 no drop set with a gain, 6 the extra nodes
+ * would change the launch plan.  classes: distinct drop sets found; taken: those given a tree, six
+ * int32 each in `taken` (the dropped subtree as a node index or ~leaf, the exit root, origin
+ * triangles, dropped triangles, nodes appended, main-tree nodes shared); budget_refused: one with
+ * a gain was left out for the LDS budget.  roots: per scene-view triangle the node its extension
+ * rays start at, 0 = the main root; view_of: per device triangle (the ids the leaves name) its
+ * scene-view triangle.  nodes_off / nodes_on: the flattened node records of the two
+ * flattens (frtx_selftest_tree_refine's layout; NULL to skip).  lds_bytes(_oct) against
+ * lds_cap(_oct): what the residency rule compares (oct: 0 without octant copies).  v / t / j_all:
+ * node visits, primitive tests and J per ray of the refinement pass's validation replay, every ray
+ * started where the kernels start it, with the exit roots ignored [0] and used [1]; v / t_ext: the
+ * same per extension ray (n_ext of the n_rays) over those alone. */
+typedef struct frt_exit_tree_info {
+    int32_t why, classes, taken, budget_refused;
+    int32_t nodes_off, n_nodes, nodes_added, depth_off, depth_on, n_rays, n_ext, reserved;
+    int64_t lds_bytes, lds_bytes_oct, lds_cap, lds_cap_oct;
+    double v_all[2], t_all[2], j_all[2], v_ext[2], t_ext[2];
+} frt_exit_tree_info;
+int frtx_selftest_exit_tree(const frt_scene_view *scene, int32_t mode, frt_exit_tree_info *out, int32_t *roots,
+                            int32_t *view_of, int32_t *taken, int32_t max_taken, float *nodes_off, float *nodes_on,
+                            int32_t max_nodes);
 /* frt_trace_device's queries through the same code on the host (host memory,
  * the same ray and hit layout), over the scene flattened as an upload would
  * flatten it (FRT_TREE_REFINE and FRT_LEAF_SIZE are read) */
