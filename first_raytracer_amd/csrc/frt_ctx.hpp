@@ -112,9 +112,9 @@ struct Residency { bool lds, oct, wide; };
 inline Residency residency(const frt_ctx *c, int flags)
 {
     Residency r;
-    r.lds = c->world_kind == FRT_WORLD_BVH && c->stack_needed < kLdsMaxDepth && c->scene_lds_bytes <= kLdsSceneBytes &&
+    r.lds = c->world_kind == FRT_WORLD_BVH && c->stack_needed < kLdsMaxDepth && lds_planar_fits(c->scene_lds_bytes) &&
             !(flags & FRT_FLAG_NO_LDS_SCENE);
-    r.oct = r.lds && !(flags & FRT_FLAG_NO_OCT) && c->scene_lds_bytes_oct <= kLdsOctBytes;
+    r.oct = r.lds && !(flags & FRT_FLAG_NO_OCT) && lds_octant_fits(c->scene_lds_bytes_oct);
     r.wide = !r.lds && c->has_bvh4 && !(flags & FRT_FLAG_BVH2) && bvh4_stack_fits(c->depth4, kBvh4LdsStack);
     return r;
 }

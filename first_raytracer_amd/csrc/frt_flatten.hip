@@ -1,25 +1,20 @@
 // frt_flatten.hip -- scene flattening on the host: DFS order, fp32 conversion
 // with outward-rounded boxes, multi-triangle leaves, the 4-wide quantized tree
-// (BVH4Q), the octant node copies, the texel conversion and the topology
-// refinement of LDS-resident trees (refine_tree).  No kernel and no
-// HIP runtime call; built with the kernel units' compiler and flags so that
-// its floating-point results do not depend on which unit holds it.  Also the
-// shadow-tree pass (shadow_tree): the occluder tree of area-light shadow rays
-// appended behind the main nodes, and the exit-tree pass (exit_tree): the
-// trees extension rays start at, behind those.
+// (BVH4Q), the octant node copies and the texel conversion.  The passes over
+// the finished tree (refinement, shadow tree, exit trees) are frt_tree_passes.hip's;
+// flatten_scene ends by calling them.  No kernel and no HIP runtime call; built
+// with the kernel units' compiler and flags so that its floating-point results
+// do not depend on which unit holds it.
 #include "frt_flatten.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <functional>
 
-#include "frt_kernels.hpp"   // the LDS budgets (kLdsSceneBytes, kLdsOctBytes, kLdsMaxDepth, oct_lds_node_slots)
-#include "host/exit_tree.hpp"
-#include "host/shadow_tree.hpp"
-#include "host/tree_refine.hpp"
+#include "frt_kernels.hpp"   // the LDS footprint rule (lds_*_bytes, lds_*_fits, kLdsMaxDepth)
+#include "frt_tree_passes.hpp"
 
 using namespace frt;
 
@@ -317,628 +312,6 @@ static void fill_octants(FlatScene &F)
         }
 }
 
-// ---- topology refinement of LDS-resident binary trees (DESIGN.md "Tree refinement") ----
-// The interior nodes above the leaves of collapse_leaves are rearranged to
-// lower the traversal cost J = V + w T (node visits and primitive tests per
-// ray) of the rays the scene's own path integrator traces: the surface area
-// heuristic prices rays uniform over the box, while these start on surfaces
-// inside the scene and a third of them are shadow rays to the lights.  Leaves,
-// their boxes and the device triangle ids (the DFS rank of the input tree) stay;
-// an interior box becomes the union of its children's padded fp32 boxes, which
-// bounds them.  The closest hit is the minimum of (t, device id) whatever the
-// visit order and a shadow ray asks only whether a hit exists (collapse_leaves,
-// trace_bvh), so every hit, film and ray count is unchanged -- only visits drop.
-//
-// kRefineW, the price of a primitive test in node visits: the VALU instructions
-// of one trip of leaf_hit's triangle loop over those of one node visit, both
-// read from the disassembly of the octant plan's path kernel (path_megakernel
-// <8, kWorldBvh2Oct, ...> of frt_render_lds.hip, the two innermost loops of
-// its step loop).  A node visit is 31: the record and ref addresses (2), 12
-// v_fma_f32, 8 v_maximum3 / v_minimum3, 4 compares, the select and store of
-// the far child (3), the select of the near one (1) and the loop test (1).  A
-// leaf trip whose triangle passes every stage of the Moller-Trumbore test --
-// in a wave, a trip where any lane does -- is 56: the determinant (12), u (11),
-// v (14), t and its interval (7), the hit update (8) and the loop count (4).
-// 56 / 31 = 1.8.
-constexpr double kRefineW = 1.8;
-// The ray samples: host replays of path::Li (path_begin / path_shade, the code the
-// kernel runs per lane) on a small frame of the scene's camera, one sample per
-// pixel, fixed seeds.  The search fits on the first and the result is judged on
-// the second, larger one, which it never saw.
-constexpr int kRefineFitFrame = 24, kRefineValFrame = 40;
-constexpr uint32_t kRefineFitSeed = 0x7ee5eed1u, kRefineValSeed = 0x7ee5eed2u;
-constexpr int kRefineMaxDepth = 33;      // the renders' default max_depth
-// Move evaluations per flatten, the pass's whole budget (no timer).  On Cornell
-// (19 leaves) the first sweep over every (subtree, place) pair takes ~600 and
-// finds all but a percent of the gain; 700 keep the pass under a frame's time
-// (0.17 s on one core against 0.23 s for the 1080p, 512 spp frame).
-constexpr int kRefineMaxEvals = 700;
-
-static bool tree_refine_knob()
-{
-    const char *e = std::getenv("FRT_TREE_REFINE");
-    return !(e && std::atoi(e) == 0);
-}
-
-// does the residency rule (frt_ctx.hpp pick_*) put this scene's binary tree in LDS?
-static bool tree_in_lds(const FlatScene &F)
-{
-    if (F.meta.world_kind != FRT_WORLD_BVH || F.meta.root < 0 || F.depth >= kLdsMaxDepth) return false;
-    const size_t bytes = sizeof(float4) * (F.nodes.size() + F.tris.size() + F.tshade.size() + F.mats.size());
-    return bytes <= kLdsSceneBytes || !F.nodes_oct.empty();
-}
-
-struct RefineLeaf { float box[6]; int ref; };   // lo xyz, hi xyz; the child ref as stored (~leaf)
-
-// the binary nodes as a topology over their leaves (interior node i = slot n_leaves + i)
-static void topology_of(const std::vector<float4> &nodes, frt_refine::Topology &t, std::vector<RefineLeaf> &leaves)
-{
-    const int nn = (int)(nodes.size() / 4);
-    leaves.clear();
-    t.child.assign(2 * (size_t)nn, 0);
-    t.n_leaves = nn + 1;
-    t.root = t.n_leaves;
-    for (int i = 0; i < nn; ++i) {
-        const float4 *n = &nodes[4 * i];
-        const float b[2][6] = {{n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y}, {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w}};
-        for (int side = 0; side < 2; ++side) {
-            const int c = f2i(side ? n[3].y : n[3].x);
-            if (c >= 0) { t.child[2 * i + side] = t.n_leaves + c; continue; }
-            RefineLeaf l;
-            for (int k = 0; k < 6; ++k) l.box[k] = b[side][k];
-            l.ref = c;
-            t.child[2 * i + side] = (int)leaves.size();
-            leaves.push_back(l);
-        }
-    }
-}
-
-// the rays of one replayed frame against the leaves
-// occl (optional): per ray of R, 1 = an area-light shadow ray (light_shadow_ray)
-// from (optional): per ray of R, the device triangle an extension ray leaves (the closest hit before
-// it), -1 for a camera ray, a shadow ray and a ray that leaves a sphere.  Every ray is traced from
-// the main root here, whatever exit roots F holds: the sample is the same with the pass on and off.
-static void sample_rays(const FlatScene &F, const std::vector<RefineLeaf> &leaves, int frame, uint32_t seed,
-                        frt_refine::RaySet &R, std::vector<uint8_t> *occl = nullptr, std::vector<float> *origins = nullptr,
-                        std::vector<int> *from = nullptr)
-{
-    const DevScene S = host_scene(F);
-    struct Ray { f3 o, d; float tmax; bool shadow, occl; int from; };
-    std::vector<Ray> rays;
-    std::vector<int> stack(std::max(F.depth + 1, 1));
-    for (int pix = 0; pix < frame * frame; ++pix) {
-        PathState<float> P;
-        path_begin<kMatsAll>(P, S, pix % frame, pix / frame, frame, frame, seed, (uint32_t)pix, 0u);
-        int last = -1;   // the primitive the path stands on
-        for (;;) {
-            rays.push_back(Ray{P.ro, P.rd, P.rtmax, P.shadow, light_shadow_ray(P),
-                               (P.shadow || last < 0 || (last & FRT_PRIM_SPHERE)) ? -1 : last});
-            const Hit<float> h = trace<FRT_WORLD_BVH, 1>(S, P.ro, P.rd, P.rtmax, P.shadow, stack.data(), light_shadow_ray(P));
-            if (!P.shadow) last = h.prim;
-            uint32_t n_ext = 0, n_sh = 0;
-            if (path_shade<kMatsAll>(P, S, h, kRefineMaxDepth, n_ext, n_sh)) break;
-        }
-    }
-    const int n = (int)rays.size(), nl = (int)leaves.size();
-    R = frt_refine::RaySet{};
-    R.n = n;
-    R.n_leaves = nl;
-    R.prim_first.assign(nl + 1, 0);
-    for (int l = 0; l < nl; ++l) {
-        const int lref = ~leaves[l].ref;
-        const bool sph = (lref & FRT_PRIM_SPHERE) != 0;
-        const int first = sph ? lref : (lref & kLeafIndexMask), count = sph ? 1 : (lref >> kLeafCountShift) + 1;
-        for (int k = 0; k < count; ++k) R.prim_ref.push_back(first + k);
-        R.prim_first[l + 1] = (int)R.prim_ref.size();
-    }
-    R.n_prims = (int)R.prim_ref.size();
-    R.tmin.resize(n); R.tmax.resize(n); R.anyhit.resize(n); R.live.resize(n);
-    if (occl) occl->assign(n, 0);
-    if (from) from->assign(n, -1);
-    if (origins) origins->clear();
-    R.slab.resize((size_t)nl * n * 6);
-    R.prim_t.resize((size_t)n * R.n_prims);
-    // rays in a scattered order (a stride coprime to n), so that every chunk of the
-    // sample holds every part of the frame and every bounce
-    int stride = (int)(0.618 * n) | 1;
-    auto gcd = [](int a, int b) { while (b) { const int c = a % b; a = b; b = c; } return a; };
-    while (n > 1 && gcd(stride, n) != 1) stride += 2;
-    for (int i = 0; i < n; ++i) {
-        const Ray &q = rays[(int)(((int64_t)i * stride) % std::max(n, 1))];
-        Trav<float> T;
-        R.live[i] = trav_begin(T, S, S.root, q.o, q.d, q.tmax) ? 1 : 0;
-        R.tmin[i] = T.tmin;
-        R.tmax[i] = q.tmax;
-        R.anyhit[i] = q.shadow ? 1 : 0;
-        if (occl) (*occl)[i] = q.occl ? 1 : 0;
-        if (from) (*from)[i] = q.from;
-        if (origins && q.occl) { origins->push_back(q.o.x); origins->push_back(q.o.y); origins->push_back(q.o.z); }
-        const float inv[3] = {T.sr.invd.x, T.sr.invd.y, T.sr.invd.z}, oi[3] = {T.sr.oinv.x, T.sr.oinv.y, T.sr.oinv.z};
-        for (int l = 0; l < nl; ++l) {
-            float *s = &R.slab[((size_t)i * nl + l) * 6];
-            for (int a = 0; a < 3; ++a) {
-                const bool neg = inv[a] < 0.0f;
-                s[a] = vfma(leaves[l].box[neg ? 3 + a : a], inv[a], oi[a]);
-                s[3 + a] = -vfma(leaves[l].box[neg ? a : 3 + a], inv[a], oi[a]);
-            }
-        }
-        for (int k = 0; k < R.n_prims; ++k) {
-            float u, v;
-            R.prim_t[(size_t)i * R.n_prims + k] = prim_t(S, R.prim_ref[k], q.o, q.d, T.tmin, q.tmax, u, v);
-        }
-    }
-}
-
-// F.nodes rewritten for topology t in pre-order: leaf boxes as they were, an
-// interior child's box the union of its children's
-static void write_topology(FlatScene &F, const frt_refine::Topology &t, const std::vector<RefineLeaf> &leaves)
-{
-    const int L = t.n_leaves, nn = L - 1;
-    std::vector<float> box(6 * (size_t)(L + nn));
-    std::function<void(int)> bound = [&](int s) {
-        float *b = &box[6 * (size_t)s];
-        if (s < L) { for (int k = 0; k < 6; ++k) b[k] = leaves[s].box[k]; return; }
-        const int c0 = t.child[2 * (s - L)], c1 = t.child[2 * (s - L) + 1];
-        bound(c0);
-        bound(c1);
-        for (int k = 0; k < 3; ++k) {
-            b[k] = std::min(box[6 * (size_t)c0 + k], box[6 * (size_t)c1 + k]);
-            b[3 + k] = std::max(box[6 * (size_t)c0 + 3 + k], box[6 * (size_t)c1 + 3 + k]);
-        }
-    };
-    bound(t.root);
-    std::vector<float4> out(4 * (size_t)nn);
-    int next = 0;
-    std::function<int(int)> emit = [&](int s) {   // returns the child ref of slot s
-        if (s < L) return leaves[s].ref;
-        const int me = next++;
-        const int c[2] = {t.child[2 * (s - L)], t.child[2 * (s - L) + 1]};
-        const float *a = &box[6 * (size_t)c[0]], *b = &box[6 * (size_t)c[1]];
-        out[4 * me + 0] = make_float4(a[0], a[1], a[2], a[3]);
-        out[4 * me + 1] = make_float4(a[4], a[5], b[0], b[1]);
-        out[4 * me + 2] = make_float4(b[2], b[3], b[4], b[5]);
-        const int r0 = emit(c[0]), r1 = emit(c[1]);
-        out[4 * me + 3] = make_float4(i2f(r0), i2f(r1), 0.0f, 0.0f);
-        return me;
-    };
-    emit(t.root);
-    F.nodes.swap(out);
-}
-
-bool tree_cost_host(const FlatScene &F, TreeCost &out)
-{
-    out = TreeCost{};
-    out.w = kRefineW;
-    if (!tree_in_lds(F) || F.nodes.empty()) return false;
-    frt_refine::Topology t;
-    std::vector<RefineLeaf> leaves;
-    topology_of(F.nodes, t, leaves);
-    frt_refine::RaySet val;
-    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, val);
-    const frt_refine::Cost c = frt_refine::tree_cost(t, val);
-    out.V = c.V; out.T = c.T; out.J = frt_refine::cost_j(c, kRefineW);
-    out.depth = t.depth();
-    out.n_rays = val.n;
-    return true;
-}
-
-// The pass itself, on a finished FlatScene.  True when F.nodes changed (the
-// caller makes the octant copies and BVH4Q again).  F.depth stays the input
-// tree's: the refined tree is never deeper, and the stack class and launch plan
-// chosen from it stay what they were.
-static bool refine_tree(FlatScene &F)
-{
-    if (!tree_in_lds(F) || F.nodes.size() / 4 < 3) return false;
-    frt_refine::Topology t;
-    std::vector<RefineLeaf> leaves;
-    topology_of(F.nodes, t, leaves);
-    const frt_refine::Topology input = t;
-    frt_refine::RaySet fit;
-    sample_rays(F, leaves, kRefineFitFrame, kRefineFitSeed, fit);
-    if (frt_refine::refine(t, fit, kRefineW, input.depth(), kRefineMaxEvals) == 0) return false;
-    // keep it only if the rays it was not fitted on agree
-    frt_refine::RaySet val;
-    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, val);
-    const double j0 = frt_refine::cost_j(frt_refine::tree_cost(input, val), kRefineW);
-    const double j1 = frt_refine::cost_j(frt_refine::tree_cost(t, val), kRefineW);
-    if (!(j1 < j0)) return false;
-    write_topology(F, t, leaves);
-    return true;
-}
-
-// ---- the occluder tree of area-light shadow rays (DESIGN.md "Shadow tree") ----
-// path::Li's and pssmlt::Li's shadow rays to a light are segments from a surface
-// point to a point on a light.  host/shadow_tree.cpp proves for each triangle
-// whether any such segment can report a hit on it (in a closed room: the walls no
-// segment crosses, the light's own plane); the leaves that keep a primitive get a
-// binary tree of their own, built from the main tree's nodes where a subtree lost
-// nothing and appended behind them in F.nodes otherwise, and trav_begin starts
-// those rays at its root.  Every other ray, and BVH4Q, keep the main root.  A
-// shadow ray asks only whether a hit exists, so films and ray counts are
-// unchanged -- only visits drop.
-static bool shadow_tree_knob()
-{
-    const char *e = std::getenv("FRT_SHADOW_TREE");
-    return !(e && std::atoi(e) == 0);
-}
-
-// sv's triangles in device order (tri_view) for the proofs of the shadow-tree and exit-tree passes,
-// which name triangles as the leaves do
-struct ProofGeometry {
-    std::vector<double> tv, tn;
-    std::vector<uint8_t> smooth;
-    frt_shadow::Geometry g;
-};
-static void proof_geometry(const frt_scene_view *sv, const FlatScene &F, ProofGeometry &pg)
-{
-    const int nt = sv->n_tris;
-    pg.tv.resize(9 * (size_t)nt);
-    pg.smooth.assign(nt, 0);
-    bool any_smooth = false;
-    for (int d = 0; d < nt; ++d) {
-        const int i = F.tri_view[d];
-        std::copy(&sv->tri_v[9 * (size_t)i], &sv->tri_v[9 * (size_t)i] + 9, &pg.tv[9 * (size_t)d]);
-        pg.smooth[d] = sv->tri_geometry_normal && !sv->tri_geometry_normal[i];
-        any_smooth |= pg.smooth[d] != 0;
-    }
-    if (any_smooth) {
-        pg.tn.resize(9 * (size_t)nt);
-        for (int d = 0; d < nt; ++d)
-            std::copy(&sv->tri_n[9 * (size_t)F.tri_view[d]], &sv->tri_n[9 * (size_t)F.tri_view[d]] + 9, &pg.tn[9 * (size_t)d]);
-    }
-    frt_shadow::Geometry &g = pg.g;
-    g.n_tris = nt; g.n_spheres = sv->n_spheres;
-    g.tri_v = pg.tv.data(); g.tri_n = any_smooth ? pg.tn.data() : nullptr; g.tri_smooth = pg.smooth.data();
-    g.sphere = sv->sphere;
-    g.lights = F.lights.data(); g.n_lights = (int)F.lights.size(); g.sphere_bit = FRT_PRIM_SPHERE;
-    for (int k = 0; k < 3; ++k) { g.cam_o[k] = sv->cam_origin[k]; g.cam_u[k] = sv->cam_u[k]; g.cam_v[k] = sv->cam_v[k]; }
-    g.lens_r = sv->cam_lens_radius;
-    g.eps = (double)Cst<float>::eps;
-}
-
-// sv's triangles in device order (tri_view) for the proof, which names triangles as the leaves do
-static void shadow_tree(const frt_scene_view *sv, FlatScene &F)
-{
-    auto &I = F.shadow;
-    DevScene &S = F.meta;
-    I.nodes_main = (int)(F.nodes.size() / 4);
-    if (sv->n_lights <= 0) { I.why = FlatScene::kShadowNoLights; return; }
-    // dielectric and the specular lobes leave from p - eps n: only lambertian / diffuse_light scenes
-    for (int i = 0; i < sv->n_materials; ++i)
-        if (sv->materials[i].type != FRT_MAT_LAMBERTIAN && sv->materials[i].type != FRT_MAT_DIFFUSE_LIGHT) {
-            I.why = FlatScene::kShadowMaterial;
-            return;
-        }
-    if (!tree_in_lds(F) || F.nodes.empty()) { I.why = FlatScene::kShadowNotResident; return; }
-    const int nt = sv->n_tris;
-    ProofGeometry pg;
-    proof_geometry(sv, F, pg);
-    const frt_shadow::Geometry &g = pg.g;
-    frt_shadow::Classified c;
-    frt_shadow::classify(g, c);
-    if (c.why != frt_shadow::kRan) {
-        I.why = c.why == frt_shadow::kNoLights ? FlatScene::kShadowNoLights : FlatScene::kShadowTooLarge;
-        return;
-    }
-    // triangles outside the tree (trailing device ids) are in no leaf; count those in one
-    int n_dropped = 0;
-    for (int d = 0; d < nt; ++d) n_dropped += c.dropped[d];
-    if (n_dropped == 0) { I.why = FlatScene::kShadowNothing; return; }
-    std::vector<float> nodes(4 * F.nodes.size());
-    memcpy(nodes.data(), F.nodes.data(), sizeof(float4) * F.nodes.size());
-    frt_shadow::Tree t;
-    frt_shadow::build(nodes, S.root, c.dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
-    if (t.dropped_leaves == 0) { I.why = FlatScene::kShadowNothing; return; }
-    // the appended nodes must leave the scene on the plan it has (pick_launcher_t reads these sizes)
-    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
-    const int nn0 = I.nodes_main, nn1 = (int)(nodes.size() / 16);
-    const bool lds0 = sizeof(float4) * (4 * (size_t)nn0 + rest) <= kLdsSceneBytes;
-    const bool lds1 = sizeof(float4) * (4 * (size_t)nn1 + rest) <= kLdsSceneBytes;
-    const bool oct0 = !F.nodes_oct.empty();
-    const bool oct1 = sizeof(float4) * (oct_lds_node_slots(nn1) + rest) <= kLdsOctBytes;
-    if (lds0 != lds1 || oct0 != oct1) { I.why = FlatScene::kShadowBudget; return; }
-    F.nodes.resize((size_t)4 * nn1);
-    memcpy(F.nodes.data(), nodes.data(), sizeof(float) * nodes.size());
-    if (oct0) F.nodes_oct.resize(8 * F.nodes.size());
-    S.sroot = t.empty ? kSentinel : t.root;   // nothing can occlude: the traversal ends at its first step
-    I.why = FlatScene::kShadowRan;
-    I.dropped = c.dropped;
-    I.n_dropped = n_dropped; I.rule_a = c.n_rule_a; I.rule_b = c.n_rule_b;
-    I.added = t.added; I.shared = t.shared; I.empty = t.empty;
-}
-
-// every node of F.nodes -- the main tree and the shadow tree's own -- as one topology over the
-// distinct leaves; slot_of_ref(ref) names a root
-static void topology_all(const std::vector<float4> &nodes, frt_refine::Topology &t, std::vector<RefineLeaf> &leaves,
-                         std::vector<int> &leaf_refs)
-{
-    const int nn = (int)(nodes.size() / 4);
-    leaves.clear();
-    leaf_refs.clear();
-    for (int i = 0; i < nn; ++i)
-        for (int side = 0; side < 2; ++side) {
-            const float4 *n = &nodes[4 * i];
-            const int c = f2i(side ? n[3].y : n[3].x);
-            if (c >= 0 || std::find(leaf_refs.begin(), leaf_refs.end(), c) != leaf_refs.end()) continue;
-            const float b[2][6] = {{n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y}, {n[1].z, n[1].w, n[2].x, n[2].y, n[2].z, n[2].w}};
-            RefineLeaf l;
-            for (int k = 0; k < 6; ++k) l.box[k] = b[side][k];
-            l.ref = c;
-            leaves.push_back(l);
-            leaf_refs.push_back(c);
-        }
-    t.n_leaves = (int)leaves.size();
-    t.root = t.n_leaves;
-    t.child.assign(2 * (size_t)nn, 0);
-    for (int i = 0; i < nn; ++i)
-        for (int side = 0; side < 2; ++side) {
-            const int c = f2i(side ? nodes[4 * i + 3].y : nodes[4 * i + 3].x);
-            t.child[2 * i + side] = c >= 0 ? t.n_leaves + c
-                                           : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), c) - leaf_refs.begin());
-        }
-}
-
-bool shadow_cost_host(const FlatScene &F, ShadowCost &out)
-{
-    out = ShadowCost{};
-    if (F.shadow.why != FlatScene::kShadowRan) return false;
-    frt_refine::Topology t;
-    std::vector<RefineLeaf> leaves;
-    std::vector<int> leaf_refs;
-    topology_all(F.nodes, t, leaves, leaf_refs);
-    frt_refine::RaySet R;
-    std::vector<uint8_t> occl;
-    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl);
-    const DevScene S = host_scene(F);
-    int n_occl = 0;
-    for (int i = 0; i < R.n; ++i) n_occl += occl[i];
-    out.n_rays = n_occl;
-    if (n_occl == 0) return true;
-    auto price = [&](int which) {   // V and T of the rays marked live, per area-light shadow ray
-        const frt_refine::Cost c = frt_refine::tree_cost(t, R);
-        out.V[which] = c.V * R.n / n_occl;
-        out.T[which] = c.T * R.n / n_occl;
-    };
-    // from the main root: the area-light shadow rays alone, those that miss the scene's box stopped there
-    for (int i = 0; i < R.n; ++i) {
-        R.live[i] = R.live[i] && occl[i];
-        if (occl[i] && !R.live[i]) ++out.stops[0];
-    }
-    price(0);
-    // from the shadow root.  trav_begin tests no box there, so every such ray is live; a ray that would
-    // miss the box of the shadow tree's leaves costs its one visit and is reported as a stop
-    if (F.shadow.empty) {   // kSentinel: done at the first step
-        out.stops[1] = n_occl;
-        return true;
-    }
-    const int sroot = S.sroot >= 0 ? t.n_leaves + S.sroot
-                                   : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), S.sroot) - leaf_refs.begin());
-    std::vector<int> under, st{sroot};   // the leaves under the shadow root
-    while (!st.empty()) {
-        const int s = st.back();
-        st.pop_back();
-        if (s < t.n_leaves) { under.push_back(s); continue; }
-        st.push_back(t.child[2 * (s - t.n_leaves)]);
-        st.push_back(t.child[2 * (s - t.n_leaves) + 1]);
-    }
-    auto misses_box = [&](int i) {   // the union of the leaves' slab records against trav_begin's interval
-        float u[6];
-        for (int k = 0; k < 6; ++k) u[k] = __builtin_inff();
-        for (int l : under)
-            for (int k = 0; k < 6; ++k) u[k] = std::min(u[k], R.slab[((size_t)i * R.n_leaves + l) * 6 + k]);
-        const float tn = std::max(std::max(u[0], u[1]), std::max(u[2], Cst<float>::eps));
-        const float tf = std::min(std::min(-u[3], -u[4]), std::min(-u[5], R.tmax[i]));
-        return !(tn <= tf);
-    };
-    R.root.assign(R.n, sroot);
-    for (int i = 0; i < R.n; ++i) {
-        R.live[i] = occl[i];
-        if (occl[i] && misses_box(i)) ++out.stops[1];
-    }
-    price(1);
-    return true;
-}
-
-void shadow_origins_host(const FlatScene &F, std::vector<float> &origins)
-{
-    origins.clear();
-    if (F.meta.world_kind != FRT_WORLD_BVH || F.nodes.empty()) return;
-    frt_refine::Topology t;
-    std::vector<RefineLeaf> leaves;
-    std::vector<int> leaf_refs;
-    topology_all(F.nodes, t, leaves, leaf_refs);
-    frt_refine::RaySet R;
-    std::vector<uint8_t> occl;
-    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl, &origins);
-}
-
-// ---- the trees extension rays start at (DESIGN.md "Exit trees") ----
-// An extension ray of a lambertian vertex leaves its triangle on the stored normal's side and
-// climbs from there; its origin lies inside the box of the leaf it leaves and of every ancestor, so
-// from the main root the first leaf it reaches is its own, two triangles in the plane it has just
-// left.  host/exit_tree.cpp proves per origin triangle which triangles such a ray cannot report a
-// hit on; per main-tree leaf the largest subtree made of those alone is its drop set (a wall: its
-// own leaf; a face of a box: the box's subtree where the tree groups the box), and the main tree
-// without it -- frt_shadow::build's rules, the copied ancestors appended behind the main and shadow
-// nodes -- is where trav_begin starts those rays.  The root's node index goes into the third word of
-// the triangle's second shading record (0 = the main root).  Closest hits are unchanged, so films
-// and ray counts are; only visits and triangle tests drop.  Among the distinct drop sets the pass
-// takes, greedily, those with the largest fall of J = V + kRefineW T on the refinement pass's
-// fitting replay per appended node, while the appended nodes leave the scene on the LDS plan it has.
-static bool exit_tree_knob()
-{
-    const char *e = std::getenv("FRT_EXIT_TREE");
-    return !(e && std::atoi(e) == 0);
-}
-
-// Blocks of the LDS plans that a CU holds: a block's LDS -- the traversal stack and the item state
-// of its 256 lanes, then the scene -- is allocated in granules of 1280 B out of 160 KiB.  Measured
-// on the Cornell octant plan (8-entry stack: 18432 B before the scene), profiles/exittree/
-// exit_cap.jsonl: a scene of 13328 B (31760 B a block, 25 granules, 5 blocks) runs the path kernel
-// in 186.6 ms and AO in 25.0 ms, one of 13712 B (32144 B, 26 granules, 4 blocks) in 209.3 ms and
-// 28.3 ms -- inside kLdsOctBytes, which the residency rule keeps.  The exit trees are worth less
-// than a block, so their nodes must leave this count where it is.
-constexpr size_t kLdsGranule = 1280, kLdsCuBytes = 160 * 1024;
-static int lds_blocks_per_cu(const FlatScene &F, size_t scene_bytes)
-{
-    const size_t stack = F.depth < 8 ? 8 : 16;   // the LDS plans' stack classes (frt_plans.hpp)
-    const size_t block = (stack + kItemWords) * kBlock * sizeof(int) + scene_bytes;
-    return (int)(kLdsCuBytes / ((block + kLdsGranule - 1) / kLdsGranule * kLdsGranule));
-}
-constexpr int kExitMaxRoot = 1 << 10;   // node indices the kernels carry above PathState::depth (kExitShift)
-
-static void exit_tree(const frt_scene_view *sv, FlatScene &F)
-{
-    auto &I = F.exit;
-    DevScene &S = F.meta;
-    I.nodes_before = (int)(F.nodes.size() / 4);
-    I.root.assign((size_t)std::max(sv->n_tris, 0), 0);
-    // dielectric and the specular lobes leave from p - eps n: only lambertian / diffuse_light scenes
-    for (int i = 0; i < sv->n_materials; ++i)
-        if (sv->materials[i].type != FRT_MAT_LAMBERTIAN && sv->materials[i].type != FRT_MAT_DIFFUSE_LIGHT) {
-            I.why = FlatScene::kExitMaterial;
-            return;
-        }
-    if (!tree_in_lds(F) || F.nodes.empty() || S.root != 0) { I.why = FlatScene::kExitNotResident; return; }
-    ProofGeometry pg;
-    proof_geometry(sv, F, pg);
-    frt_exit::Hidden hid;
-    frt_exit::classify(pg.g, hid);
-    if (hid.why != frt_exit::kRan) { I.why = FlatScene::kExitTooLarge; return; }
-    std::vector<float> nodes(4 * F.nodes.size());
-    memcpy(nodes.data(), F.nodes.data(), sizeof(float4) * F.nodes.size());
-    std::vector<frt_exit::Class> cls;
-    frt_exit::classes(nodes, S.root, FRT_PRIM_SPHERE, kLeafCountShift, hid, cls);
-    I.classes = (int)cls.size();
-    if (cls.empty()) { I.why = FlatScene::kExitNothing; return; }
-
-    // the fitting replay against the leaves, with the triangle every extension ray leaves
-    frt_refine::Topology t0;
-    std::vector<RefineLeaf> leaves;
-    std::vector<int> leaf_refs;
-    topology_all(F.nodes, t0, leaves, leaf_refs);
-    frt_refine::RaySet R;
-    std::vector<int> from;
-    sample_rays(F, leaves, kRefineFitFrame, kRefineFitSeed, R, nullptr, nullptr, &from);
-    const std::vector<uint8_t> live0 = R.live;
-
-    // each class alone: its tree on a copy of the nodes, the nodes it appends and the fall of J
-    struct Cand { int cls, added; double gain; };
-    std::vector<Cand> cand;
-    auto as_float4 = [](const std::vector<float> &v) {
-        std::vector<float4> o(v.size() / 4);
-        memcpy(o.data(), v.data(), sizeof(float) * v.size());
-        return o;
-    };
-    for (int c = 0; c < (int)cls.size(); ++c) {
-        std::vector<float> trial = nodes;
-        frt_shadow::Tree t;
-        frt_shadow::build(trial, S.root, cls[c].dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
-        if (t.empty || t.root <= 0 || t.root >= kExitMaxRoot || t.dropped_leaves == 0) continue;
-        frt_refine::Topology tt;
-        std::vector<RefineLeaf> l2;
-        std::vector<int> r2;
-        topology_all(as_float4(trial), tt, l2, r2);
-        if (r2 != leaf_refs) continue;   // (appended nodes name the main tree's leaves only)
-        bool any = false;
-        for (int i = 0; i < R.n; ++i) {
-            const bool mine = from[i] >= 0 && std::binary_search(cls[c].members.begin(), cls[c].members.end(), from[i]);
-            R.live[i] = live0[i] && mine;
-            any |= R.live[i] != 0;
-        }
-        if (!any) continue;
-        R.root.clear();
-        const double j0 = frt_refine::cost_j(frt_refine::tree_cost(tt, R), kRefineW);
-        R.root.assign(R.n, tt.n_leaves + t.root);
-        const double j1 = frt_refine::cost_j(frt_refine::tree_cost(tt, R), kRefineW);
-        if (j1 < j0) cand.push_back(Cand{c, t.added, j0 - j1});
-    }
-    if (cand.empty()) { I.why = FlatScene::kExitNothing; return; }
-    // by gain per appended node (a tree that appends nothing first), then gain, then class order
-    std::stable_sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) {
-        if ((a.added == 0) != (b.added == 0)) return a.added == 0;
-        const double ra = a.gain / std::max(a.added, 1), rb = b.gain / std::max(b.added, 1);
-        if (ra != rb) return ra > rb;
-        return a.gain > b.gain;
-    });
-    // the appended nodes must leave the scene on the plan it has (pick_launcher_t reads these sizes)
-    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
-    const int nn0 = I.nodes_before;
-    const bool lds0 = sizeof(float4) * (4 * (size_t)nn0 + rest) <= kLdsSceneBytes;
-    const bool oct0 = !F.nodes_oct.empty();
-    auto planar = [&](int nn) { return sizeof(float4) * (4 * (size_t)nn + rest); };
-    auto octant = [&](int nn) { return sizeof(float4) * (oct_lds_node_slots(nn) + rest); };
-    auto fits = [&](int nn1) {
-        const bool lds1 = planar(nn1) <= kLdsSceneBytes;
-        const bool oct1 = octant(nn1) <= kLdsOctBytes;
-        if (lds0 != lds1 || oct0 != oct1) return false;
-        // ... and with as many blocks on a CU (lds_blocks_per_cu)
-        if (lds0 && lds_blocks_per_cu(F, planar(nn1)) != lds_blocks_per_cu(F, planar(nn0))) return false;
-        return !oct0 || lds_blocks_per_cu(F, octant(nn1)) == lds_blocks_per_cu(F, octant(nn0));
-    };
-    bool refused = false;
-    for (const Cand &k : cand) {
-        const frt_exit::Class &c = cls[k.cls];
-        std::vector<float> next = nodes;
-        frt_shadow::Tree t;
-        frt_shadow::build(next, S.root, c.dropped, FRT_PRIM_SPHERE, kLeafCountShift, t);
-        if (!fits((int)(next.size() / 16)) || t.root >= kExitMaxRoot) { refused = true; continue; }
-        nodes.swap(next);
-        for (int d : c.members) I.root[d] = t.root;
-        I.taken.push_back({c.sub, t.root, (int)c.members.size(), c.n_dropped, t.added, t.shared, k.gain});
-        I.added += t.added;
-    }
-    if (I.taken.empty()) { I.why = refused ? FlatScene::kExitBudget : FlatScene::kExitNothing; return; }
-    I.budget_refused = refused;
-    F.nodes.resize(nodes.size() / 4);
-    memcpy(F.nodes.data(), nodes.data(), sizeof(float) * nodes.size());
-    if (oct0) F.nodes_oct.resize(8 * F.nodes.size());
-    for (size_t d = 0; d < I.root.size(); ++d)
-        if (I.root[d]) F.tshade[2 * d + 1].z = i2f(I.root[d]);
-    I.why = FlatScene::kExitRan;
-}
-
-bool exit_cost_host(const FlatScene &F, ExitCost &out)
-{
-    out = ExitCost{};
-    if (!tree_in_lds(F) || F.nodes.empty()) return false;
-    frt_refine::Topology t;
-    std::vector<RefineLeaf> leaves;
-    std::vector<int> leaf_refs;
-    topology_all(F.nodes, t, leaves, leaf_refs);
-    frt_refine::RaySet R;
-    std::vector<uint8_t> occl;
-    std::vector<int> from;
-    sample_rays(F, leaves, kRefineValFrame, kRefineValSeed, R, &occl, nullptr, &from);
-    const DevScene S = host_scene(F);
-    auto slot = [&](int ref) {
-        return ref >= 0 ? t.n_leaves + ref : (int)(std::find(leaf_refs.begin(), leaf_refs.end(), ref) - leaf_refs.begin());
-    };
-    const std::vector<uint8_t> live0 = R.live;
-    out.n_rays = R.n;
-    for (int i = 0; i < R.n; ++i) out.n_ext += from[i] >= 0;
-    for (int on = 0; on < 2; ++on) {
-        // every ray where the kernels start it: area-light shadow rays at the shadow root (trav_begin
-        // tests no box there; an empty shadow tree ends them at once), extension rays at their exit root
-        R.root.assign(R.n, t.root);
-        R.live = live0;
-        for (int i = 0; i < R.n; ++i) {
-            if (occl[i] && S.sroot != S.root) {
-                if (S.sroot == kSentinel) R.live[i] = 0;
-                else { R.root[i] = slot(S.sroot); R.live[i] = 1; }
-            } else if (on && from[i] >= 0 && from[i] < (int)F.exit.root.size() && F.exit.root[from[i]]) {
-                R.root[i] = slot(F.exit.root[from[i]]);
-            }
-        }
-        const frt_refine::Cost all = frt_refine::tree_cost(t, R);
-        out.V_all[on] = all.V; out.T_all[on] = all.T; out.J_all[on] = frt_refine::cost_j(all, kRefineW);
-        for (int i = 0; i < R.n; ++i) R.live[i] = R.live[i] && from[i] >= 0;
-        const frt_refine::Cost ext = frt_refine::tree_cost(t, R);
-        if (out.n_ext > 0) { out.V_ext[on] = ext.V * R.n / out.n_ext; out.T_ext[on] = ext.T * R.n / out.n_ext; }
-    }
-    return true;
-}
-
 int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine, int shadow, int exit)
 {
     auto fail = [&](int code, const std::string &m) { err = m; return code; };
@@ -1070,8 +443,9 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
             const std::vector<float4> binary = F.nodes;
             const int depth = F.depth;
             collapse_leaves(F, kLeafSmallScene);
-            const size_t bytes = sizeof(float4) * (F.nodes.size() + 5 * (size_t)nt + 2 * (size_t)nm);
-            if (bytes > kLdsSceneBytes || F.depth >= kLdsMaxDepth) {
+            // (2 float4s per material undercounts them: kMatStride is 5.  Counting them right changes
+            // which scenes get two-triangle leaves, so it is a change of its own.)
+            if (!lds_planar_fits(lds_planar_bytes(F.nodes.size() / 4, 5 * (size_t)nt + 2 * (size_t)nm)) || F.depth >= kLdsMaxDepth) {
                 F.nodes = binary;
                 F.depth = depth;
                 collapse_leaves(F, kLeafDefault);
@@ -1198,9 +572,8 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     // octant copies of the binary nodes: child boxes as (near xyz, far xyz).
     // Only the LDS binary plan reads them, and only when they fit its budget
     // (pick_launcher_t): larger scenes get none (8x the node array otherwise).
-    const size_t oct_bytes = sizeof(float4) * (oct_lds_node_slots((int)(F.nodes.size() / 4)) + F.tris.size() +
-                                               F.tshade.size() + F.mats.size());
-    if (sv->world_kind == FRT_WORLD_BVH && F.depth < kLdsMaxDepth && oct_bytes <= kLdsOctBytes)
+    if (sv->world_kind == FRT_WORLD_BVH && F.depth < kLdsMaxDepth &&
+        lds_octant_fits(lds_octant_bytes(F.nodes.size() / 4, lds_rest(F))))
         F.nodes_oct.resize(8 * F.nodes.size());
     S.root = (sv->world_kind == FRT_WORLD_BVH) ? ((sv->root >= 0) ? 0 : ~dev_ref(~sv->root)) : 0;
     S.sroot = S.root;   // until the shadow-tree pass finds one
@@ -1237,19 +610,13 @@ int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool
     S.cam64_h = d3d(sv->cam_horizontal); S.cam64_v = d3d(sv->cam_vertical);
     S.cam64_u = d3d(sv->cam_u); S.cam64_vv = d3d(sv->cam_v);
     S.lens_r64 = sv->cam_lens_radius;
-    // topology refinement (refine_tree): needs the finished scene for its ray sample, so the
-    // derived trees are made again from the nodes it rewrote
-    bool again = (refine < 0 ? tree_refine_knob() : refine != 0) && refine_tree(F);
-    // the shadow tree over the tree the main rays will walk: its nodes go behind the main ones
-    if (shadow < 0 ? shadow_tree_knob() : shadow != 0) {
-        shadow_tree(sv, F);
-        again |= F.shadow.why == FlatScene::kShadowRan;
-    }
-    // the exit trees over the same tree: their nodes go behind the shadow tree's
-    if (exit < 0 ? exit_tree_knob() : exit != 0) {
-        exit_tree(sv, F);
-        again |= F.exit.why == FlatScene::kExitRan;
-    }
+    // The passes over the tree (frt_tree_passes.hip) need the finished scene for their ray samples, so
+    // the derived trees are made again from the nodes they rewrote: the refinement of the main tree,
+    // the shadow tree over the tree the main rays will walk, its nodes behind the main ones, and the
+    // exit trees over the same tree, their nodes behind the shadow tree's.
+    bool again = refine_tree(F, refine);
+    again |= shadow_tree(sv, F, shadow);
+    again |= exit_tree(sv, F, exit);
     if (again) derive_trees();
     S.n_nodes = (int)(F.nodes.size() / 4);
     return FRT_OK;

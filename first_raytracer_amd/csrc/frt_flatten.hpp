@@ -24,7 +24,7 @@ struct FlatScene {
     std::vector<int> tri_view;      // device triangle id -> scene-view triangle (DevScene::tri_view)
     DevScene meta{};     // scalars + camera; pointers filled by the consumer
     int depth = 0;
-    // what the shadow-tree pass did (frt_flatten.hip shadow_tree): why != kShadowRan leaves
+    // what the shadow-tree pass did (frt_tree_passes.hip shadow_tree): why != kShadowRan leaves
     // meta.sroot the main root and `nodes` untouched
     enum { kShadowRan = 0, kShadowOff, kShadowNoLights, kShadowTooLarge, kShadowMaterial, kShadowNotResident,
            kShadowNothing, kShadowBudget };
@@ -34,7 +34,7 @@ struct FlatScene {
         int n_dropped = 0, rule_a = 0, rule_b = 0, nodes_main = 0, added = 0, shared = 0;
         bool empty = false;
     } shadow;
-    // what the exit-tree pass did (frt_flatten.hip exit_tree): why != kExitRan leaves `nodes` and the
+    // what the exit-tree pass did (frt_tree_passes.hip exit_tree): why != kExitRan leaves `nodes` and the
     // shading records untouched (every exit root 0 = the main root)
     enum { kExitRan = 0, kExitOff, kExitMaterial, kExitNotResident, kExitTooLarge, kExitNothing, kExitBudget };
     struct ExitClass { int sub, root, members, dropped, added, shared; double gain; };   // sub: the dropped subtree (node, or ~leaf)
@@ -49,30 +49,9 @@ struct FlatScene {
 };
 
 // f64: also build the fp64 records of the fp64 kernels (DESIGN.md "Precision")
-// refine: the topology refinement of LDS-resident binary trees; -1 = as FRT_TREE_REFINE says
-// (default on, read at each call), 0 = off, 1 = on
-// shadow: the occluder tree of area-light shadow rays behind the main nodes, the same way (FRT_SHADOW_TREE)
-// exit: the trees extension rays start at, behind those, the same way (FRT_EXIT_TREE)
+// refine, shadow, exit: the modes of the passes over the finished tree (frt_tree_passes.hpp)
 int flatten_scene(const frt_scene_view *sv, FlatScene &F, std::string &err, bool f64, int refine = -1, int shadow = -1,
                   int exit = -1);
-// V, T and J of the refinement pass's validation rays, each started where the kernels start it, with
-// the exit roots ignored (index 0) and used (1): over all rays, and V and T over the extension rays
-// alone (per extension ray); false when the tree is not LDS-resident
-struct ExitCost {
-    double V_all[2] = {0, 0}, T_all[2] = {0, 0}, J_all[2] = {0, 0}, V_ext[2] = {0, 0}, T_ext[2] = {0, 0};
-    int n_rays = 0, n_ext = 0;
-};
-bool exit_cost_host(const FlatScene &F, ExitCost &out);
-// V and T of the refinement pass's validation rays that are area-light shadow rays, started at the
-// main root (index 0) and at the shadow root (1); stops: how many of them miss that root's box
-struct ShadowCost { double V[2] = {0, 0}, T[2] = {0, 0}; int n_rays = 0, stops[2] = {0, 0}; };
-bool shadow_cost_host(const FlatScene &F, ShadowCost &out);
-// the origins of those rays (3 floats each), for the segment property test
-void shadow_origins_host(const FlatScene &F, std::vector<float> &origins);
-// traversal cost of F's binary tree on the refinement pass's validation rays (the counting
-// self-test); false when the tree is not LDS-resident, so the pass does not apply
-struct TreeCost { double V = 0.0, T = 0.0, J = 0.0, w = 0.0; int depth = 0, n_rays = 0; };
-bool tree_cost_host(const FlatScene &F, TreeCost &out);
 // frt_set_env_image / the self-test: validate the image and convert it
 int env_texels_of(const frt_image *img, std::vector<float4> &out, std::string &err);
 // host image of the flattened scene as the kernels see it (HBM strides)

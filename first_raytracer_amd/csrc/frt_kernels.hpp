@@ -164,6 +164,26 @@ struct ItemState {
     __device__ void set(int k, int x) const { b[k * kBlock] = x; }
 };
 
+// ---- the LDS footprint rule (host side) ----
+// What scene_to_lds copies and the kernels lay out, in bytes, and whether it is within the budgets.
+// Every place that asks "which plan does this scene get" -- the upload, the launch plans, the tree
+// passes that append nodes, the self-tests -- asks here.
+// rest: the float4s behind the nodes (triangles, shading records, materials)
+constexpr size_t lds_planar_bytes(size_t n_nodes, size_t rest) { return sizeof(float4) * (4 * n_nodes + rest); }
+constexpr size_t lds_octant_bytes(size_t n_nodes, size_t rest)
+{
+    return sizeof(float4) * (oct_lds_node_slots((int)n_nodes) + rest);
+}
+constexpr bool lds_planar_fits(size_t bytes) { return bytes <= kLdsSceneBytes; }
+constexpr bool lds_octant_fits(size_t bytes) { return bytes <= kLdsOctBytes; }
+// a block's LDS: the traversal stack (list worlds have none) and the item state of its lanes, then the scene
+constexpr size_t lds_block_bytes(size_t stack, size_t scene_bytes, bool has_stack = true)
+{
+    return (has_stack ? stack * kBlock * sizeof(int) : 0) + (size_t)kItemWords * kBlock * sizeof(int) + scene_bytes;
+}
+// the rest of a FlatScene
+template <class Scene> size_t lds_rest(const Scene &F) { return F.tris.size() + F.tshade.size() + F.mats.size(); }
+
 // R: float (the product kernels) or double (the fp64 kernels, DESIGN.md
 // "Precision": list worlds under FRT_PRECISION_AUTO, every plan under _FP64)
 template <int STACK, int WORLD, bool LDS_SCENE, int WAVES = 1, int MATS = kMatsNone,

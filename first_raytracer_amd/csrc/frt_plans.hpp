@@ -54,8 +54,7 @@ static Launcher make_launcher(size_t scene_bytes)
     Launcher L;
     L.fn = reinterpret_cast<const void *>(&path_megakernel<STACK, WORLD, LDS, WAVES, MATS, KIND, R>);
     L.f64 = kIsF64<R>;
-    L.lds = (WORLD != FRT_WORLD_LIST ? (size_t)STACK * kBlock * sizeof(int) : 0) +
-            (size_t)kItemWords * kBlock * sizeof(int) + (LDS ? scene_bytes : 0);
+    L.lds = lds_block_bytes(STACK, LDS ? scene_bytes : 0, WORLD != FRT_WORLD_LIST);
     L.scene_lds = LDS ? scene_bytes : 0;
     L.stack = STACK;
     L.waves = WAVES > 1 ? WAVES : 0;

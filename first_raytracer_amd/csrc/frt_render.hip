@@ -332,10 +332,8 @@ extern "C" int frt_upload_scene(frt_ctx *c, const frt_scene_view *sv)
     }
     c->has_spec_mats = c->mats != kMatsNone;
     c->depth4 = F.depth4;
-    c->scene_lds_bytes = sizeof(float4) * (F.nodes.size() + F.tris.size() + F.tshade.size() + F.mats.size());
-    c->scene_lds_bytes_oct = F.nodes_oct.empty() ? SIZE_MAX
-                             : sizeof(float4) * (oct_lds_node_slots(S.n_nodes) + F.tris.size() + F.tshade.size() +
-                                                 F.mats.size());
+    c->scene_lds_bytes = lds_planar_bytes(S.n_nodes, lds_rest(F));
+    c->scene_lds_bytes_oct = F.nodes_oct.empty() ? SIZE_MAX : lds_octant_bytes(S.n_nodes, lds_rest(F));
     c->has_f64 = want_f64;
     c->have_scene = true;
     return FRT_OK;

@@ -223,7 +223,7 @@ SparseLauncher make_sparse()
 {
     SparseLauncher L;
     L.fn = reinterpret_cast<const void *>(&film_reduce::sparse_kernel<STACK, WORLD, MATS, KIND, R>);
-    L.lds = (WORLD != FRT_WORLD_LIST ? (size_t)STACK * kBlock * sizeof(int) : 0) + (size_t)kItemWords * kBlock * sizeof(int);
+    L.lds = lds_block_bytes(STACK, 0, WORLD != FRT_WORLD_LIST);   // the scene stays in HBM
     L.stack = STACK;
     L.wide = WORLD == kWorldBvh4;
     L.f64 = kIsF64<R>;

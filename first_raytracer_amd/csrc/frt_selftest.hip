@@ -8,6 +8,7 @@
 
 #include "frt_ctx.hpp"
 #include "frt_flatten.hpp"
+#include "frt_tree_passes.hpp"
 #include "host/envdist.hpp"
 
 using namespace frt;
@@ -179,7 +180,7 @@ extern "C" int frt_selftest_mlt_paths_host(const frt_scene_view *sv, int nx, int
     return FRT_OK;
 }
 
-// Counting hook of the tree refinement pass (frt_flatten.hip refine_tree): the
+// Counting hook of the tree refinement pass (frt_tree_passes.hip refine_tree): the
 // scene flattened without and with the pass, both trees priced on the pass's
 // validation rays, and the flattened node records for structure checks.
 extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost out[2], float *nodes_off,
@@ -204,7 +205,7 @@ extern "C" int frtx_selftest_tree_refine(const frt_scene_view *sv, frt_tree_cost
     return FRT_OK;
 }
 
-// Counting hook of the shadow-tree pass (frt_flatten.hip shadow_tree): what it dropped and built,
+// Counting hook of the shadow-tree pass (frt_tree_passes.hip shadow_tree): what it dropped and built,
 // the traversal cost of the area-light shadow rays from either root, and the segment property test
 extern "C" int frtx_selftest_shadow_tree(const frt_scene_view *sv, frt_shadow_tree_info *out, uint8_t *dropped,
                                          float *nodes, int32_t max_nodes, int64_t segments, uint32_t seed)
@@ -262,7 +263,7 @@ extern "C" int frtx_selftest_shadow_tree(const frt_scene_view *sv, frt_shadow_tr
     return FRT_OK;
 }
 
-// Counting hook of the exit-tree pass (frt_flatten.hip exit_tree): the scene flattened without the
+// Counting hook of the exit-tree pass (frt_tree_passes.hip exit_tree): the scene flattened without the
 // pass and with it (mode: -1 as FRT_EXIT_TREE says, 0 off, 1 on), what the pass took, the root of
 // every triangle, and the traversal cost of the validation rays with the roots ignored and used
 extern "C" int frtx_selftest_exit_tree(const frt_scene_view *sv, int32_t mode, frt_exit_tree_info *out, int32_t *roots,
@@ -285,9 +286,8 @@ extern "C" int frtx_selftest_exit_tree(const frt_scene_view *sv, int32_t mode, f
     out->nodes_added = I.added;
     out->budget_refused = I.budget_refused ? 1 : 0;
     out->depth_off = F0.depth; out->depth_on = F.depth;
-    const size_t rest = F.tris.size() + F.tshade.size() + F.mats.size();
-    out->lds_bytes = (int64_t)(sizeof(float4) * (F.nodes.size() + rest));
-    out->lds_bytes_oct = F.nodes_oct.empty() ? 0 : (int64_t)(sizeof(float4) * (oct_lds_node_slots(out->n_nodes) + rest));
+    out->lds_bytes = (int64_t)lds_planar_bytes(out->n_nodes, lds_rest(F));
+    out->lds_bytes_oct = F.nodes_oct.empty() ? 0 : (int64_t)lds_octant_bytes(out->n_nodes, lds_rest(F));
     out->lds_cap = (int64_t)kLdsSceneBytes; out->lds_cap_oct = (int64_t)kLdsOctBytes;
     if (out->nodes_off > max_nodes || out->n_nodes > max_nodes) return FRT_E_INVALID;
     if (nodes_off) memcpy(nodes_off, F0.nodes.data(), F0.nodes.size() * sizeof(float4));

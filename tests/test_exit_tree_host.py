@@ -1,4 +1,4 @@
-"""The exit-tree pass (FRT_EXIT_TREE; csrc/frt_flatten.hip exit_tree, csrc/host/exit_tree.cpp) on the host:
+"""The exit-tree pass (FRT_EXIT_TREE; csrc/frt_tree_passes.hip exit_tree, csrc/host/exit_tree.cpp) on the host:
 which subtree each triangle's extension rays skip, the trees it appends, what the counter says it saves,
 and that films and ray counts do not depend on it.  CPU only."""
 import os

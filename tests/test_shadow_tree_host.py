@@ -1,4 +1,4 @@
-"""The shadow-tree pass (FRT_SHADOW_TREE; csrc/frt_flatten.hip shadow_tree, csrc/host/shadow_tree.cpp)
+"""The shadow-tree pass (FRT_SHADOW_TREE; csrc/frt_tree_passes.hip shadow_tree, csrc/host/shadow_tree.cpp)
 on the host: which triangles it proves no area-light shadow segment can hit, the tree it appends, what
 the counter says it saves, and that films and ray counts do not depend on it.  CPU only."""
 import os

@@ -1,4 +1,4 @@
-"""The tree refinement pass (FRT_TREE_REFINE; csrc/frt_flatten.hip refine_tree,
+"""The tree refinement pass (FRT_TREE_REFINE; csrc/frt_tree_passes.hip refine_tree,
 csrc/host/tree_refine.cpp) on the host: the interior nodes of an LDS-resident
 binary tree are rearranged, so the tree's structure, every hit, every film and
 the counted traversal cost are compared with the pass on and off."""
