@@ -445,6 +445,7 @@ class HostScene:
         return {
             "tri_v": arr(v.tri_v, v.n_tris, np.float64, 9),
             "tri_material": arr(v.tri_material, v.n_tris, np.int32),
+            "sphere": arr(v.sphere, v.n_spheres, np.float64, 4),
             "node_box": arr(v.node_box, v.n_nodes, np.float64, 6),
             "node_child": arr(v.node_child, v.n_nodes, np.int32, 2),
             "root": v.root,

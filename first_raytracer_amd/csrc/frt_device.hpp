@@ -291,8 +291,15 @@ template <typename R> FRT_HD V3<R> normalize(V3<R> v) { return rlen(v) * v; }
 // (one FMA per slab plane).  Zero direction components are nudged to
 // +-1e-30 so no 0*inf NaN can arise; the reference's NaN-tolerant compare
 // (aabb.h:24-25) keeps the interval unchanged in that case, and so does this
-// (the near-parallel slab spans +-huge).  Device boxes are padded outward, so
-// neither the nudge nor the FMA rounding can cull a hit.
+// (the near-parallel slab spans +-huge).  Device boxes are padded outward
+// (flatten_scene: 4e-6 of the scene's size), which covers the nudge and the
+// FMA rounding for origins inside the scene's root box or at camera distance
+// from it: there a tree returns the list's closest hit bit for bit
+// (tests/test_trace_exact_host.py, test_gpu_trace_exact.py, at the shipped
+// cameras and inside the box).  It is no unconditional guarantee: the rounding
+// of oinv = -o * invd grows with |o|, so from far away hits near silhouettes
+// and edges can be culled, at a rate that grows with |o| / scene extent
+// (DESIGN.md section 3 has the measured table).
 // a value every active lane holds, moved into a scalar register (plain on the host)
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ int frt_uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }

@@ -273,7 +273,9 @@ FRT_HD bool leaf_hit(const DevScene &S, int lref, V3<R> o, V3<R> d, R tmin, bool
 // parallel_bvh_node::hit as an ordered stack traversal.  Closest hit keeps the
 // reference's answer: minimum t, exact ties to the leaf that comes first in
 // the left-first DFS (device triangle ids ARE that order).  Boxes are padded
-// outward, so culling never removes a hit.
+// outward, so culling removes no hit of a ray that starts inside the scene's
+// root box or at camera distance from it (tested there: slab_ray's comment,
+// frt_device.hpp); from far origins it can, DESIGN.md section 3.
 //
 // The traversal is resumable: Trav holds a ray's whole traversal state, and
 // one bvh*_step call descends to the next leaf and tests it.  The megakernel

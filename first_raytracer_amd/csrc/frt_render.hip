@@ -436,11 +436,15 @@ struct TraceLauncher {
     int waves = 0;
     bool lds_scene = false;
     size_t scene_lds = 0;   // as Launcher::scene_lds
+    int stack = 0;          // per-lane stack entries of the plan (0: a list world has none)
+    bool wide = false;      // the 4-wide tree
 };
 template <int STACK, int WORLD, bool LDS, int WAVES>
 static TraceLauncher make_trace(size_t scene_bytes)
 {
     TraceLauncher L;
+    L.stack = WORLD != FRT_WORLD_LIST ? STACK : 0;
+    L.wide = WORLD == kWorldBvh4;
     L.fn = reinterpret_cast<const void *>(&trace_kernel<STACK, WORLD, LDS, WAVES>);
     L.lds = (WORLD != FRT_WORLD_LIST ? (size_t)STACK * kBlock * sizeof(int) : 0) + (LDS ? scene_bytes : 0);
     L.scene_lds = LDS ? scene_bytes : 0;
@@ -513,6 +517,8 @@ extern "C" int frt_trace_device(frt_ctx *c, const float *rays, int64_t n, float 
         st->kernel_ms = ms;
         st->scene_in_lds = L.lds_scene ? 1u : 0u;
         st->waves_cap = (uint32_t)L.waves;
+        st->stack_entries = (uint32_t)L.stack;
+        st->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
         st->scene_bytes = L.lds_scene ? L.scene_lds : c->scene_lds_bytes;   // what this plan reads
         st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }

@@ -441,7 +441,18 @@ int frt_mlt_chain_state(frt_ctx *ctx, uint64_t first, uint64_t n, float *u_out, 
  * as int32 bits: the scene view's triangle index or FRT_PRIM_SPHERE | k, -1 =
  * miss; a miss leaves t = t_max).  flags: FRT_FLAG_NO_LDS_SCENE / _BVH2 /
  * _NO_OCT choose the plan as for frt_render.  Returns after the work has
- * completed on `hip_stream` (NULL = the context's stream); st->kernel_ms.
+ * completed on `hip_stream` (NULL = the context's stream); st: kernel_ms,
+ * camera_rays = n, and the plan that ran (scene_in_lds, waves_cap,
+ * stack_entries -- 0 for a list world --, bvh_depth, scene_bytes).
+ * What a tree plan answers: for origins inside the scene's root box or at
+ * camera distance from it, the closest hit of the list of the same primitives,
+ * bit for bit in t (and in u, v with the same primitive; primitives at one t
+ * tie by DFS order, not list order), except below the BVH's own t_min.  That
+ * is tested inside the box and at the shipped cameras.  It is not guaranteed
+ * beyond: the slab test's rounding grows with |origin|, so from far away hits
+ * near silhouettes and edges can be lost, at a rate that grows with |origin| /
+ * scene extent (measured: none of 20,000 rays at 50 scene
+ * sizes, 0.3 to 3 % of the rays aimed at exact vertices at 500).
  * The ray queue has its own word in the context, apart from the render's, but
  * a context is still one stream's worth of state: calls on one context are
  * issued from one host thread, one at a time (each returns when its work is
