@@ -244,7 +244,8 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
 # further self-test hooks (frt.h "frtx_*"): beside the frt_* entry points, not among them
 EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
              "frtx_selftest_plan", "frtx_selftest_shadow_tree", "frtx_render_pixels", "frtx_render_pixels_device",
-             "frtx_selftest_exit_tree")
+             "frtx_selftest_exit_tree", "frtx_radiance_rays", "frtx_radiance_rays_device", "frtx_camera_rays_device",
+             "frtx_selftest_radiance_host", "frtx_selftest_camera_rays_host")
 
 
 def lib():
@@ -324,6 +325,15 @@ def lib():
     L.frtx_render_pixels.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, ctypes.POINTER(Stats)]
     L.frtx_render_pixels_device.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, vp,
                                             ctypes.POINTER(Stats)]
+    if hasattr(L, "frtx_radiance_rays"):   # (FRT_LIB_PATH may name an earlier revision's build for a timing A/B)
+        L.frtx_radiance_rays.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, ctypes.POINTER(Stats)]
+        L.frtx_radiance_rays_device.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp, vp,
+                                                ctypes.POINTER(Stats)]
+        L.frtx_camera_rays_device.argtypes = [vp, ctypes.POINTER(RenderParams), vp, ctypes.c_int64, vp, vp]
+        L.frtx_selftest_radiance_host.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp, ctypes.c_int64,
+                                                  ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
+        L.frtx_selftest_camera_rays_host.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp,
+                                                     ctypes.c_int64, vp]
     _lib = L
     return L
 
@@ -333,6 +343,8 @@ def _check(rc, what, ctx=None):
         msg = ""
         if ctx is not None:
             msg = lib().frt_last_error(ctx).decode(errors="replace")
+        elif "_rays" in what or "radiance" in what:   # hooks without a context: frt_last_error(NULL) has their text
+            msg = lib().frt_last_error(None).decode(errors="replace")
         raise FrtError(f"{what} failed: {ERRORS.get(rc, rc)} {msg}")
 
 
@@ -484,6 +496,7 @@ class Context:
 
     def __init__(self, device=0, precision=None):
         self.ptr = ctypes.c_void_p()
+        self.device = int(device)
         _check(lib().frt_create(int(device), ctypes.byref(self.ptr)), f"frt_create(device={device})")
         if precision is not None:
             self.set_precision(precision)
@@ -564,6 +577,54 @@ class Context:
                                         V.ctypes.data if variance else None, ctypes.byref(st)),
                "frtx_render_pixels", self.ptr)
         return rgb, V, st
+
+    def radiance_rays(self, params, rays, variance=True):
+        """frtx_radiance_rays: the radiance along caller-supplied first rays through this
+        library's integrator (path or ao).  rays: (n, 8) float32, frt_trace_device's record --
+        origin, t_max of the first segment, direction (any length), and in word 7 the entry's RNG
+        stream id as uint32 bits (ray_records() builds them; entries with equal ids share their
+        random numbers).  Per entry the mean of Li over samples [sample_offset, sample_offset +
+        spp), every sample along the same first ray, and the batch-means V of render_pixels.
+        nx, ny and tile_size of `params` are ignored.
+        Returns (rgb (n, 3) float32, V (n, 3) float32 or None, stats)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        rgb = np.zeros((len(rays), 3), np.float32)
+        V = np.zeros((len(rays), 3), np.float32) if variance else None
+        st = Stats()
+        _check(lib().frtx_radiance_rays(self.ptr, ctypes.byref(params), rays.ctypes.data, len(rays), rgb.ctypes.data,
+                                        V.ctypes.data if variance else None, ctypes.byref(st)),
+               "frtx_radiance_rays", self.ptr)
+        return rgb, V, st
+
+    def camera_rays(self, params, pixels):
+        """frtx_camera_rays_device: the first rays the scene's own camera makes for the listed
+        pixels of the nx x ny frame at sample `sample_offset` (fp32; FRT_FLAG_SOBOL selects that
+        sampler's film and lens points), as (n, 8) float32 records with the pixel as stream id --
+        radiance_rays of them at spp = 1 is render_pixels of the pixels.  The list and the
+        records pass through device memory (torch)."""
+        import torch
+        pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+        dev = torch.device("cuda", self.device)
+        px = torch.from_numpy(pixels).to(dev)
+        out = torch.zeros((len(pixels), 8), dtype=torch.float32, device=dev)
+        _check(lib().frtx_camera_rays_device(self.ptr, ctypes.byref(params), px.data_ptr(), len(pixels), out.data_ptr(), None),
+               "frtx_camera_rays_device", self.ptr)
+        return out.cpu().numpy()
+
+    def render_camera(self, params, make_rays, passes=1):
+        """An image through a camera of the caller's: make_rays(jitter) -> (n, 8) ray records
+        (first_raytracer_amd.cameras), jitter a (2,) offset in [0, 1)^2 inside the texel.  Pass k
+        of `passes` renders spp samples at sample_offset = k * spp along rays jittered by a pair
+        hashed from (seed, k) -- pass 0 of a single pass takes the texel centres -- and the passes
+        are combined by film_accumulate's rule.  Returns (rgb (n, 3) float32, stats of the last pass)."""
+        acc, st = None, None
+        for k in range(int(passes)):
+            p = RenderParams.from_buffer_copy(params)
+            p.sample_offset = params.sample_offset + k * params.spp
+            jitter = None if passes == 1 else np.random.default_rng([int(params.seed), k]).random(2)
+            rgb, _, st = self.radiance_rays(p, make_rays(jitter), variance=False)
+            acc = rgb if acc is None else film_accumulate(acc, k * params.spp, rgb, params.spp)
+        return acc, st
 
     def render_until(self, params, target, max_spp, first_spp=None, adaptive=False, switch=None):
         """Progressive render of `params` (path or ao; spp and sample_offset are the driver's) that
@@ -881,6 +942,46 @@ def selftest_path_host(scene, params, pixels, env_image=None):
                                             ctypes.byref(desc), out.ctypes.data, ctypes.byref(st)),
            "frt_selftest_path_host_env")
     return out, st
+
+
+def ray_records(origins, directions, t_max=None, streams=None):
+    """(n, 8) float32 ray records for Context.radiance_rays / trace_device: origins and
+    directions (n, 3) (either may be one row for all), t_max (scalar or (n,); None: FLT_MAX, the
+    camera rays' own), streams (n,) uint32 RNG stream ids (None: arange(n))."""
+    o, d = np.broadcast_arrays(np.asarray(origins, np.float32).reshape(-1, 3), np.asarray(directions, np.float32).reshape(-1, 3))
+    rec = np.zeros((len(d), 8), np.float32)
+    rec[:, 0:3] = o
+    rec[:, 3] = np.finfo(np.float32).max if t_max is None else t_max
+    rec[:, 4:7] = d
+    ids = np.arange(len(d), dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32).reshape(-1)
+    rec.view(np.uint32)[:, 7] = ids
+    return rec
+
+
+def selftest_radiance_host(scene, params, rays, env_image=None):
+    """Context.radiance_rays through the same per-lane code on the host (frtx_selftest_radiance_host):
+    the refusals of the entry point, then ray_begin and the host replay's loop.  Returns (rgb, stats)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros((len(rays), 3), np.float32)
+    st = Stats()
+    view = scene.view()
+    desc = None
+    if env_image is not None:
+        a, fmt = image_array({"data": env_image})
+        desc = ctypes.byref(Image(a.shape[1], a.shape[0], fmt, 0, a.ctypes.data))
+    _check(lib().frtx_selftest_radiance_host(ctypes.byref(view), ctypes.byref(params), rays.ctypes.data, len(rays), desc,
+                                             out.ctypes.data, ctypes.byref(st)), "frtx_selftest_radiance_host")
+    return out, st
+
+
+def selftest_camera_rays_host(scene, params, pixels):
+    """Context.camera_rays on the host (frtx_selftest_camera_rays_host): (n, 8) float32 records."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+    out = np.zeros((len(pixels), 8), np.float32)
+    view = scene.view()
+    _check(lib().frtx_selftest_camera_rays_host(ctypes.byref(view), ctypes.byref(params), pixels.ctypes.data, len(pixels),
+                                                out.ctypes.data), "frtx_selftest_camera_rays_host")
+    return out
 
 
 def selftest_tree_refine(scene):

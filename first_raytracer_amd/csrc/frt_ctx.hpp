@@ -77,6 +77,7 @@ struct frt_ctx {
     unsigned long long *sp_wave_rays = nullptr; size_t sp_wave_rays_bytes = 0;
     int32_t *sp_pixels = nullptr; size_t sp_pixels_bytes = 0;
     float *sp_out = nullptr; size_t sp_out_bytes = 0;
+    float *sp_rays = nullptr; size_t sp_rays_bytes = 0;   // frtx_radiance_rays: the host call's device copy of its list
 };
 
 #pragma GCC visibility push(hidden)

@@ -1039,6 +1039,27 @@ FRT_HD void path_begin(PathState<R> &P, const DevScene &S, int px, int py, int n
     P.prev_spec = false;
 }
 
+// A caller's first ray (frtx_radiance_rays, frt.h) in path_begin's place: the record's two float4
+// -- (origin, t_max of the first segment), (direction, stream id as uint32 bits) -- widened to R,
+// the key with the stream id in the pixel's place, the rest as path_begin leaves it: a camera ray
+// (depth 0, prev_spec false).  Dimensions 0-3 (film, lens) are not read.
+template <int MATS = kMatsNone, typename R>
+FRT_HD void ray_begin(PathState<R> &P, float4 a, float4 b, uint32_t seed, uint32_t sample)
+{
+    P.key = smp_key<MATS>(seed, (uint32_t)f2i(b.w), sample);
+    P.ro = V3<R>{R(a.x), R(a.y), R(a.z)};
+    P.rd = V3<R>{R(b.x), R(b.y), R(b.z)};
+    P.rtmax = R(a.w);
+    P.shadow = false;
+    P.term = false;
+    P.depth = 0;
+    P.beta = V3<R>{R(1), R(1), R(1)};
+    P.L = zero3<R>();
+    P.prev_pdf = R(0);
+    P.prev_p = zero3<R>();
+    P.prev_spec = false;
+}
+
 // The ray P holds is an area-light shadow ray of path::Li / pssmlt::Li: a segment to a point on a
 // light (t_max below 1), not the environment-NEE ray (t_max = Cst::tmax).  Not for ao_shade's rays.
 template <typename R> FRT_HD bool light_shadow_ray(const PathState<R> &P) { return P.shadow && P.rtmax < R(1); }

@@ -15,6 +15,7 @@
 
 #include "frt_kernels.hpp"
 #include "frt_plans.hpp"
+#include "frt_rays.hpp"
 #include "frt_flatten.hpp"
 #include "frt_lbvh.hpp"
 #include "host/envdist.hpp"
@@ -151,6 +152,7 @@ extern "C" int frt_destroy(frt_ctx *c)
     if (c->sp_wave_rays) (void)hipFree(c->sp_wave_rays);
     if (c->sp_pixels) (void)hipFree(c->sp_pixels);
     if (c->sp_out) (void)hipFree(c->sp_out);
+    if (c->sp_rays) (void)hipFree(c->sp_rays);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -158,7 +160,17 @@ extern "C" int frt_destroy(frt_ctx *c)
     return FRT_OK;
 }
 
-extern "C" const char *frt_last_error(const frt_ctx *c) { return c ? c->err.c_str() : "null context"; }
+// without a context: the last refusal of a frtx_*_rays call made without one (frt_rays.hpp), if any
+std::string &frt::null_ctx_err()
+{
+    static thread_local std::string e;
+    return e;
+}
+extern "C" const char *frt_last_error(const frt_ctx *c)
+{
+    if (c) return c->err.c_str();
+    return frt::null_ctx_err().empty() ? "null context" : frt::null_ctx_err().c_str();
+}
 
 // Precision of the context's kernels (DESIGN.md "Precision"): read by the
 // next frt_upload_scene (which then also uploads the fp64 records) and by

@@ -20,6 +20,13 @@
 // The unit compiles in parts (FRT_SPARSE_PART, Makefile) so that the parts build side by side:
 // 0 = the C-ABI, the reduce kernel, the lambertian and AO kernels; 1, 2, 3 = the path kernels of
 // kMatsAll, kMatsAll | kMatsEnv, and the sampled image.  Without the macro it is one unit.
+//
+// frtx_radiance_rays / frtx_radiance_rays_device / frtx_camera_rays_device (frt.h):
+// the same loop over a list of caller-supplied first rays.  The list's kind is a compile-time
+// parameter of the loop (SRC), so the pixel kernels compile to what they were; the ray kernels
+// (sparse_kernel<..., kSrcRays>, the same 114 rungs x material sets) are parts 4 .. 7, cut as 0 .. 3 are.
+// Their C-ABI and the camera-ray kernel stand in part 0 beside the pixel list's, whose request
+// check, buffers, queue word and reduce kernel they share.
 #undef FRT_DIAG
 #include <hip/hip_runtime.h>
 
@@ -32,11 +39,13 @@
 #include "frt_kernels.hpp"
 #include "frt_plans.hpp"
 #include "frt_error.hpp"
+#include "frt_rays.hpp"
 
+// part 4 * SRC + k holds piece k of the kernels of source SRC
 #ifdef FRT_SPARSE_PART
-#define FRT_SPARSE_HAS(k) (FRT_SPARSE_PART == (k))
+#define FRT_SPARSE_HAS(src, k) (FRT_SPARSE_PART == 4 * (src) + (k))
 #else
-#define FRT_SPARSE_HAS(k) 1
+#define FRT_SPARSE_HAS(src, k) 1
 #endif
 
 #pragma GCC visibility push(hidden)
@@ -47,13 +56,27 @@ struct SparseLauncher {
     int stack = 0;
     bool wide = false, f64 = false;
 };
+// what a list's entries are: pixels of the frame (frtx_render_pixels) or first rays (frtx_radiance_rays)
+constexpr int kSrcPixels = 0, kSrcRays = 1;
+// the lambertian path kernels and the AO kernels (env: the context has an image)
+template <int SRC> int pick_base(const frt_ctx *c, int integrator, int flags, bool f64, bool env, SparseLauncher &L);   // piece 0
 // the path kernels of the material sets with every material, one function a part
-int pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // part 1
-int pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);   // part 2
-int pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // part 3
+template <int SRC> int pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // piece 1
+template <int SRC> int pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);   // piece 2
+template <int SRC> int pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // piece 3
+#define FRT_SPARSE_DECLARE(SRC)                                                                   \
+    template <> int pick_base<SRC>(const frt_ctx *, int, int, bool, bool, SparseLauncher &);      \
+    template <> int pick_all<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);             \
+    template <> int pick_all_env<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);         \
+    template <> int pick_nee<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);
+FRT_SPARSE_DECLARE(kSrcPixels)
+FRT_SPARSE_DECLARE(kSrcRays)
+#undef FRT_SPARSE_DECLARE
 }  // namespace frt_sparse
 #pragma GCC visibility pop
 using frt_sparse::SparseLauncher;
+using frt_sparse::kSrcPixels;
+using frt_sparse::kSrcRays;
 
 namespace {
 
@@ -67,7 +90,10 @@ struct SparseWork {
     int spi, n_chunks;
     uint32_t npix, npad, n_items;        // list entries, ... padded to 64, npad * n_chunks
     int trav_min, min_desc;
-    const int32_t *pixels;               // [npix] linear pixel y * nx + x
+    union {                              // the list, by the kernel's SRC
+        const int32_t *pixels;           // [npix] linear pixel y * nx + x
+        const float4 *rays;              // [npix][2] frt_trace_device's record: (origin, t_max), (direction, stream id)
+    };
     float *partial;                      // [n_chunks][npad][3]; padding entries are never written
     unsigned *counter;
     unsigned long long *wave_rays;       // [n_waves][4]: camera, extension, shadow, samples
@@ -86,7 +112,10 @@ namespace film_reduce {
 // path_megakernel's loop (frt_kernels.hpp) over a pixel list: the per-sample plan (a sample's
 // radiance is summed in P.L and rounded into the item's fp32 sum when the sample ends), the
 // scene from HBM, the item state and the stack columns in LDS
-template <int STACK, int WORLD, int MATS, int KIND, typename R>
+// SRC = kSrcRays: the list holds first rays.  A sample starts with ray_begin on its entry's record
+// (read again at every start: 32 bytes that stay in L2, against a path's traversal), the stream
+// id of the record keys its RNG, and the item state keeps no pixel (kIsPix, kIsPx, kIsPy unused).
+template <int STACK, int WORLD, int MATS, int KIND, typename R, int SRC = kSrcPixels>
 __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const SparseWork W)
 {
     extern __shared__ __attribute__((aligned(16))) int lds_mem[];
@@ -175,15 +204,18 @@ __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const
                     const uint32_t entry = (q / (uint32_t)W.n_chunks) * 64u + (w & 63u);
                     if (entry < W.npix) {   // padding entries of the last block carry no work
                         have_item = true;
-                        const int pix = W.pixels[entry];
+                        int pix = 0;
+                        if constexpr (SRC == kSrcPixels) pix = W.pixels[entry];
                         const int s_cur = (int)chunk * W.spi;
                         I.set(kIsCur, s_cur);
                         I.set(kIsSlot, (int)entry);
                         I.set(kIsChunk, (int)chunk);
-                        I.set(kIsPix, pix);
+                        if constexpr (SRC == kSrcPixels) I.set(kIsPix, pix);
                         I.set(kIsEnd, min(W.spp, s_cur + W.spi));
-                        I.set(kIsPx, pix % W.nx);
-                        I.set(kIsPy, pix / W.nx);
+                        if constexpr (SRC == kSrcPixels) {
+                            I.set(kIsPx, pix % W.nx);
+                            I.set(kIsPy, pix / W.nx);
+                        }
                         I.set(kIsAcc + 0, 0); I.set(kIsAcc + 1, 0); I.set(kIsAcc + 2, 0);
                     }
                 }
@@ -192,8 +224,13 @@ __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const
         const bool start = !active && have_item && I.get(kIsCur) < I.get(kIsEnd);
         if (start) {
             const int s_cur = I.get(kIsCur);
-            path_begin<MATS>(P, S, I.get(kIsPx), I.get(kIsPy), W.nx, W.ny, W.seed, (uint32_t)I.get(kIsPix),
-                             (uint32_t)s_cur + W.s_off);
+            if constexpr (SRC == kSrcPixels) {
+                path_begin<MATS>(P, S, I.get(kIsPx), I.get(kIsPy), W.nx, W.ny, W.seed, (uint32_t)I.get(kIsPix),
+                                 (uint32_t)s_cur + W.s_off);
+            } else {
+                const float4 *q = W.rays + 2 * (size_t)(uint32_t)I.get(kIsSlot);
+                ray_begin<MATS>(P, q[0], q[1], W.seed, (uint32_t)s_cur + W.s_off);
+            }
             I.set(kIsCur, s_cur + 1);
             active = true;
             next_ray = true;
@@ -218,11 +255,11 @@ __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const
 
 }  // namespace film_reduce
 
-template <int STACK, int WORLD, int MATS, int KIND, typename R>
+template <int STACK, int WORLD, int MATS, int KIND, typename R, int SRC>
 SparseLauncher make_sparse()
 {
     SparseLauncher L;
-    L.fn = reinterpret_cast<const void *>(&film_reduce::sparse_kernel<STACK, WORLD, MATS, KIND, R>);
+    L.fn = reinterpret_cast<const void *>(&film_reduce::sparse_kernel<STACK, WORLD, MATS, KIND, R, SRC>);
     L.lds = lds_block_bytes(STACK, 0, WORLD != FRT_WORLD_LIST);   // the scene stays in HBM
     L.stack = STACK;
     L.wide = WORLD == kWorldBvh4;
@@ -231,14 +268,14 @@ SparseLauncher make_sparse()
 }
 
 // the rung of the context's scene with the scene in HBM
-template <int MATS, int KIND>
+template <int MATS, int KIND, int SRC>
 int sparse_plan(const frt_ctx *c, int flags, bool f64, SparseLauncher &L)
 {
     if (f64) {   // plan_f64's rungs
         if constexpr (KIND == FRT_INTEGRATOR_PATH) {
-            if (c->world_kind == FRT_WORLD_LIST) L = make_sparse<16, FRT_WORLD_LIST, MATS, KIND, double>();
-            else if (c->stack_needed < 32) L = make_sparse<32, FRT_WORLD_BVH, MATS, KIND, double>();
-            else if (c->stack_needed < 64) L = make_sparse<64, FRT_WORLD_BVH, MATS, KIND, double>();
+            if (c->world_kind == FRT_WORLD_LIST) L = make_sparse<16, FRT_WORLD_LIST, MATS, KIND, double, SRC>();
+            else if (c->stack_needed < 32) L = make_sparse<32, FRT_WORLD_BVH, MATS, KIND, double, SRC>();
+            else if (c->stack_needed < 64) L = make_sparse<64, FRT_WORLD_BVH, MATS, KIND, double, SRC>();
             else return FRT_E_UNSUPPORTED;
             return FRT_OK;
         } else {
@@ -250,52 +287,75 @@ int sparse_plan(const frt_ctx *c, int flags, bool f64, SparseLauncher &L)
         if constexpr (Rg::lds) {
             return FRT_E_UNSUPPORTED;   // not reached: the flag forces HBM residency
         } else {
-            L = make_sparse<Rg::stack, Rg::world, MATS, KIND, float>();
+            L = make_sparse<Rg::stack, Rg::world, MATS, KIND, float, SRC>();
             return FRT_OK;
         }
     });
 }
-template <int BASE>
+template <int BASE, int SRC>
 int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
 {
     switch (features) {
-    case 0: return sparse_plan<BASE, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
-    case kMatsRoulette: return sparse_plan<BASE | kMatsRoulette, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
-    case kMatsSobol: return sparse_plan<BASE | kMatsSobol, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
-    default: return sparse_plan<BASE | kMatsSobol | kMatsRoulette, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    case 0: return sparse_plan<BASE, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);
+    case kMatsRoulette: return sparse_plan<BASE | kMatsRoulette, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);
+    case kMatsSobol: return sparse_plan<BASE | kMatsSobol, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);
+    default: return sparse_plan<BASE | kMatsSobol | kMatsRoulette, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);
     }
 }
 
 }  // namespace
 
-#if FRT_SPARSE_HAS(1)
-int frt_sparse::pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
-{
-    return sparse_plan_features<kMatsAll>(c, flags, f64, features, L);
-}
+// the pieces of one source: 0 lambertian and AO, 1 .. 3 the material sets with every material
+#define FRT_SPARSE_PIECE0(SRC)                                                                                                   \
+    template <> int frt_sparse::pick_base<SRC>(const frt_ctx *c, int integrator, int flags, bool f64, bool env, SparseLauncher &L) \
+    {                                                                                                                            \
+        if (integrator == FRT_INTEGRATOR_AO)                                                                                     \
+            return env ? sparse_plan<kMatsAll | kMatsEnv, FRT_INTEGRATOR_AO, SRC>(c, flags, false, L)                            \
+                       : sparse_plan<kMatsAll, FRT_INTEGRATOR_AO, SRC>(c, flags, false, L);                                      \
+        return sparse_plan<kMatsNone, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);                                               \
+    }
+#define FRT_SPARSE_PIECE(NAME, BASE, SRC)                                                                        \
+    template <> int frt_sparse::NAME<SRC>(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L) \
+    {                                                                                                            \
+        return sparse_plan_features<BASE, SRC>(c, flags, f64, features, L);                                      \
+    }
+#if FRT_SPARSE_HAS(0, 0)
+FRT_SPARSE_PIECE0(kSrcPixels)
 #endif
-#if FRT_SPARSE_HAS(2)
-int frt_sparse::pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
-{
-    return sparse_plan_features<kMatsAll | kMatsEnv>(c, flags, f64, features, L);
-}
+#if FRT_SPARSE_HAS(0, 1)
+FRT_SPARSE_PIECE(pick_all, kMatsAll, kSrcPixels)
 #endif
-#if FRT_SPARSE_HAS(3)
-int frt_sparse::pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
-{
-    return sparse_plan_features<kMatsAll | kMatsEnv | kMatsEnvNee>(c, flags, f64, features, L);
-}
+#if FRT_SPARSE_HAS(0, 2)
+FRT_SPARSE_PIECE(pick_all_env, kMatsAll | kMatsEnv, kSrcPixels)
+#endif
+#if FRT_SPARSE_HAS(0, 3)
+FRT_SPARSE_PIECE(pick_nee, kMatsAll | kMatsEnv | kMatsEnvNee, kSrcPixels)
+#endif
+#if FRT_SPARSE_HAS(1, 0)
+FRT_SPARSE_PIECE0(kSrcRays)
+#endif
+#if FRT_SPARSE_HAS(1, 1)
+FRT_SPARSE_PIECE(pick_all, kMatsAll, kSrcRays)
+#endif
+#if FRT_SPARSE_HAS(1, 2)
+FRT_SPARSE_PIECE(pick_all_env, kMatsAll | kMatsEnv, kSrcRays)
+#endif
+#if FRT_SPARSE_HAS(1, 3)
+FRT_SPARSE_PIECE(pick_nee, kMatsAll | kMatsEnv | kMatsEnvNee, kSrcRays)
 #endif
 
-#if FRT_SPARSE_HAS(0)
+#if FRT_SPARSE_HAS(0, 0)
 namespace {
 
 namespace film_reduce {   // see sparse_kernel
 // entry i of the list: mean = sum over chunks (fixed order) * (1 / spp), film_reduce's arithmetic,
 // and V per channel through frt_error.hpp.  Entries i >= npix (padding) are never read.
+// divide (the ray lists): mean = sum / spp, correctly rounded, so that a ray whose every sample
+// returns the same exactly-summed value (a light seen directly) returns it exactly at any spp;
+// 1 / spp is rounded unless spp is a power of two.  The same value at spp = 1.
 __global__ __launch_bounds__(256) void sparse_reduce(const float *__restrict__ partial, float *__restrict__ out_rgb,
                                                      float *__restrict__ out_var, uint32_t npix, uint32_t npad, int n_chunks,
-                                                     int spp, int spi)
+                                                     int spp, int spi, int divide)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= npix) return;
@@ -312,24 +372,45 @@ __global__ __launch_bounds__(256) void sparse_reduce(const float *__restrict__ p
     }
     const float k = 1.0f / (float)spp;
     for (int ch = 0; ch < 3; ++ch) {
-        out_rgb[3ull * i + ch] = sum[ch] * k;
+        out_rgb[3ull * i + ch] = divide ? sum[ch] / (float)spp : sum[ch] * k;
         if (out_var) out_var[3ull * i + ch] = chunk_var_result(a[ch], n_chunks, spp);
     }
 }
 
+// frtx_camera_rays_device: entry i = the first ray path_begin<MATS, float> makes for pixel pixels[i]
+// at one sample, as frt_trace_device's record (t_max = the kernels' Cst<float>::tmax, word 7 = the pixel)
+template <int MATS>
+__global__ __launch_bounds__(256) void camera_rays(const DevScene S, const int32_t *__restrict__ pixels, uint32_t npix, int nx,
+                                                   int ny, uint32_t seed, uint32_t sample, float4 *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const int pix = pixels[i];
+    PathState<float> P;
+    path_begin<MATS>(P, S, pix % nx, pix / nx, nx, ny, seed, (uint32_t)pix, sample);
+    out[2ull * i] = make_float4(P.ro.x, P.ro.y, P.ro.z, P.rtmax);
+    out[2ull * i + 1] = make_float4(P.rd.x, P.rd.y, P.rd.z, i2f(pix));
+}
+
 }  // namespace film_reduce
 
+// a refusal of the ray entry points: the context's text, or frt_last_error(NULL)'s without one
+int ray_err(frt_ctx *c, int code, const std::string &m)
+{
+    if (!c) frt::null_ctx_err() = m;
+    return set_err(c, code, m);
+}
+
+template <int SRC>
 int pick_sparse(const frt_ctx *c, int integrator, int flags, bool f64, bool env_sampling, SparseLauncher &L)
 {
     const bool env = c->env_texels != nullptr;
-    if (integrator == FRT_INTEGRATOR_AO)
-        return env ? sparse_plan<kMatsAll | kMatsEnv, FRT_INTEGRATOR_AO>(c, flags, false, L)
-                   : sparse_plan<kMatsAll, FRT_INTEGRATOR_AO>(c, flags, false, L);
+    if (integrator == FRT_INTEGRATOR_AO) return frt_sparse::pick_base<SRC>(c, integrator, flags, false, env, L);
     const int features = ((flags & FRT_FLAG_ROULETTE) ? kMatsRoulette : 0) | ((flags & FRT_FLAG_SOBOL) ? kMatsSobol : 0);
-    if (env_sampling) return frt_sparse::pick_nee(c, flags, f64, features, L);
-    if (env) return frt_sparse::pick_all_env(c, flags, f64, features, L);
-    if (c->mats != kMatsNone || features) return frt_sparse::pick_all(c, flags, f64, features, L);
-    return sparse_plan<kMatsNone, FRT_INTEGRATOR_PATH>(c, flags, f64, L);
+    if (env_sampling) return frt_sparse::pick_nee<SRC>(c, flags, f64, features, L);
+    if (env) return frt_sparse::pick_all_env<SRC>(c, flags, f64, features, L);
+    if (c->mats != kMatsNone || features) return frt_sparse::pick_all<SRC>(c, flags, f64, features, L);
+    return frt_sparse::pick_base<SRC>(c, integrator, flags, f64, env, L);
 }
 
 template <typename T>
@@ -346,38 +427,43 @@ int grow(frt_ctx *c, T *&buf, size_t &have, size_t bytes)
 }
 
 // what can be refused without a context or a device: the request and the list (host memory)
+// (rays: frtx_radiance_rays asks -- its name in the texts, which a call without a context keeps too)
 int check_request(frt_ctx *c, const frt_render_params *p, const int32_t *pixels_host, int64_t npix, int *spi, int *n_chunks,
-                  bool want_var)
+                  bool want_var, bool rays = false)
 {
-    if (!p || npix < 0) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
+    const std::string who = rays ? "radiance_rays" : "render_pixels";
+    auto set_err = [rays](frt_ctx *ctx, int code, const std::string &m) { return rays ? ray_err(ctx, code, m) : ::set_err(ctx, code, m); };
+    if (!p || npix < 0) return set_err(c, FRT_E_INVALID, who + ": bad arguments");
     const int k = p->integrator;
     if (k == FRT_INTEGRATOR_NORMALS || k == FRT_INTEGRATOR_ALBEDO || k == FRT_INTEGRATOR_DEPTH)
-        return set_err(c, FRT_E_UNSUPPORTED, "render_pixels: path and ao only (normals, albedo and depth have no sparse kernel)");
+        return set_err(c, FRT_E_UNSUPPORTED, who + ": path and ao only (normals, albedo and depth have no sparse kernel)");
     if (k != FRT_INTEGRATOR_PATH && k != FRT_INTEGRATOR_AO)
-        return set_err(c, FRT_E_INVALID, "render_pixels: path and ao only (pssmlt is no per-pixel estimator; denoise and error "
-                                         "are films of a whole frame)");
+        return set_err(c, FRT_E_INVALID, who + ": path and ao only (pssmlt is no per-pixel estimator; denoise and error "
+                                               "are films of a whole frame)");
     if (p->shard_count != 1)
-        return set_err(c, FRT_E_INVALID, "render_pixels: shard_count must be 1 (split the list instead)");
+        return set_err(c, FRT_E_INVALID, who + ": shard_count must be 1 (split the list instead)");
     frt_render_params q = *p;
     q.tile_size = 0;   // ignored here
     if (!params_ok(&q)) return set_err(c, FRT_E_INVALID, "bad render params");
     *spi = p->samples_per_item > 0 ? std::min(p->samples_per_item, p->spp) : std::max(1, p->spp / 16);
     *n_chunks = (p->spp + *spi - 1) / *spi;
     if (want_var && *n_chunks < 2)
-        return set_err(c, FRT_E_INVALID, "render_pixels: the variance needs at least 2 chunks a pixel; pass samples_per_item "
-                                         "< spp (e.g. spp / 2)");
+        return set_err(c, FRT_E_INVALID, who + ": the variance needs at least 2 chunks a pixel; pass samples_per_item "
+                                               "< spp (e.g. spp / 2)");
     if (pixels_host) {
         const int64_t n = (int64_t)p->nx * p->ny;
         for (int64_t i = 0; i < npix; ++i)
             if (pixels_host[i] < 0 || pixels_host[i] >= n)
-                return set_err(c, FRT_E_INVALID, "render_pixels: entry " + std::to_string(i) + " is pixel " +
+                return set_err(c, FRT_E_INVALID, who + ": entry " + std::to_string(i) + " is pixel " +
                                                      std::to_string(pixels_host[i]) + ", outside [0, nx * ny)");
     }
     return FRT_OK;
 }
 
 // the list, the outputs: device memory; the request is checked
-int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, int spi, int n_chunks,
+// SRC = kSrcRays: `list` holds npix ray records (checked) instead of pixels
+template <int SRC>
+int sparse_impl(frt_ctx *c, const frt_render_params *p, const void *list, int64_t npix, int spi, int n_chunks,
                 float *out_rgb, float *out_var, hipStream_t st, frt_stats *stats)
 {
     const auto t_start = std::chrono::steady_clock::now();
@@ -393,7 +479,7 @@ int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, i
         return set_err(c, FRT_E_INVALID, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
                                          "before frt_upload_scene");
     SparseLauncher L;
-    if (pick_sparse(c, p->integrator, p->flags, f64, env_sampling, L) != FRT_OK || !L.fn)
+    if (pick_sparse<SRC>(c, p->integrator, p->flags, f64, env_sampling, L) != FRT_OK || !L.fn)
         return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
     int bpc = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, L.fn, kBlock, L.lds) != hipSuccess || bpc <= 0) bpc = 1;
@@ -404,7 +490,8 @@ int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, i
     const uint32_t grab = kQueueGrab;
     // the 32-bit queue head runs past n_items by at most one grab per wave (render_impl's check)
     if (n_items + (uint64_t)n_waves * (grab + 64) >= 0xffffffffULL)
-        return set_err(c, FRT_E_UNSUPPORTED, "render_pixels: list too long for one call: split it");
+        return set_err(c, FRT_E_UNSUPPORTED, std::string(SRC == kSrcRays ? "radiance_rays" : "render_pixels") +
+                                                 ": list too long for one call: split it");
     if (const int rc = grow(c, c->sp_partial, c->sp_partial_bytes, (size_t)n_items * 3 * sizeof(float))) return rc;
     if (const int rc = grow(c, c->sp_wave_rays, c->sp_wave_rays_bytes, n_waves * 4 * sizeof(unsigned long long))) return rc;
     SparseWork W{};
@@ -414,7 +501,9 @@ int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, i
     W.npix = (uint32_t)npix; W.npad = (uint32_t)npad; W.n_items = (uint32_t)n_items;
     W.trav_min = trav_min(false, p->integrator == FRT_INTEGRATOR_PATH);
     W.min_desc = min_desc(false);
-    W.pixels = pixels; W.partial = c->sp_partial;
+    if constexpr (SRC == kSrcRays) W.rays = static_cast<const float4 *>(list);
+    else W.pixels = static_cast<const int32_t *>(list);
+    W.partial = c->sp_partial;
     W.counter = c->counter + kSparseCounterWord;   // a queue word of its own
     W.wave_rays = c->sp_wave_rays;
     W.grab = grab;
@@ -425,7 +514,7 @@ int sparse_impl(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, i
     const hipError_t le = hipLaunchKernel(L.fn, dim3(grid), dim3(kBlock), args, L.lds, st);
     if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("sparse_kernel launch: ") + hipGetErrorString(le));
     hipLaunchKernelGGL(film_reduce::sparse_reduce, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, c->sp_partial, out_rgb, out_var,
-                       W.npix, W.npad, n_chunks, p->spp, spi);
+                       W.npix, W.npad, n_chunks, p->spp, spi, SRC == kSrcRays ? 1 : 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, st));
     std::vector<unsigned long long> wr(n_waves * 4);
@@ -470,7 +559,7 @@ extern "C" int frtx_render_pixels_device(frt_ctx *c, const frt_render_params *p,
     HIPCHK(c, hipMemcpyAsync(host.data(), pixels, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
     if (const int rc = check_request(c, p, host.data(), npix, &spi, &n_chunks, out_var != nullptr)) return rc;
-    return sparse_impl(c, p, pixels, npix, spi, n_chunks, out_rgb, out_var, stream, st);
+    return sparse_impl<kSrcPixels>(c, p, pixels, npix, spi, n_chunks, out_rgb, out_var, stream, st);
 }
 
 extern "C" int frtx_render_pixels(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, float *out_rgb,
@@ -489,11 +578,107 @@ extern "C" int frtx_render_pixels(frt_ctx *c, const frt_render_params *p, const 
     if (const int rc = grow(c, c->sp_pixels, c->sp_pixels_bytes, (size_t)npix * sizeof(int32_t))) return rc;
     if (const int rc = grow(c, c->sp_out, c->sp_out_bytes, 2 * n3 * sizeof(float))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->sp_pixels, pixels, (size_t)npix * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    const int rc = sparse_impl(c, p, c->sp_pixels, npix, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
+    const int rc = sparse_impl<kSrcPixels>(c, p, c->sp_pixels, npix, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
                                c->stream, st);
     if (rc != FRT_OK) return rc;
     HIPCHK(c, hipMemcpy(out_rgb, c->sp_out, n3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_var) HIPCHK(c, hipMemcpy(out_var, c->sp_out + n3, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+
+// ---- a list of first rays (frt.h frtx_radiance_rays) ----
+namespace {
+
+// the request and, when it is in host memory, the list
+int check_rays(frt_ctx *c, const frt_render_params *p, const float *rays_host, int64_t n, int *spi, int *n_chunks, bool want_var)
+{
+    if (!p || n < 0) return ray_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
+    frt_render_params q = *p;
+    q.nx = q.ny = 1;   // ignored here, as tile_size is
+    if (const int rc = check_request(c, &q, nullptr, n, spi, n_chunks, want_var, true)) return rc;
+    if (rays_host) {
+        std::string why;
+        if (frt::rays_first_bad(rays_host, n, why) >= 0) return ray_err(c, FRT_E_INVALID, "radiance_rays: " + why);
+    }
+    return FRT_OK;
+}
+
+}  // namespace
+
+extern "C" int frtx_radiance_rays_device(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
+                                         float *out_var, void *hip_stream, frt_stats *st)
+{
+    int spi = 0, n_chunks = 0;
+    if (const int rc = check_rays(c, p, nullptr, n, &spi, &n_chunks, out_var != nullptr)) return rc;
+    if (!c) return ray_err(c, FRT_E_INVALID, "radiance_rays: null context");
+    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+    if (st) memset(st, 0, sizeof(*st));
+    if (n == 0) return FRT_OK;
+    if (!rays || !out_rgb) return set_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the list is read back and checked before any kernel runs
+    std::vector<float> host((size_t)n * 8);
+    HIPCHK(c, hipMemcpyAsync(host.data(), rays, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    if (const int rc = check_rays(c, p, host.data(), n, &spi, &n_chunks, out_var != nullptr)) return rc;
+    return sparse_impl<kSrcRays>(c, p, rays, n, spi, n_chunks, out_rgb, out_var, stream, st);
+}
+
+extern "C" int frtx_radiance_rays(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
+                                  float *out_var, frt_stats *st)
+{
+    int spi = 0, n_chunks = 0;
+    if (n > 0 && !rays) return ray_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
+    if (const int rc = check_rays(c, p, rays, n, &spi, &n_chunks, out_var != nullptr)) return rc;
+    if (!c) return ray_err(c, FRT_E_INVALID, "radiance_rays: null context");
+    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+    if (st) memset(st, 0, sizeof(*st));
+    if (n == 0) return FRT_OK;
+    if (!out_rgb) return set_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n3 = (size_t)n * 3, ray_bytes = (size_t)n * 8 * sizeof(float);
+    if (const int rc = grow(c, c->sp_rays, c->sp_rays_bytes, ray_bytes)) return rc;
+    if (const int rc = grow(c, c->sp_out, c->sp_out_bytes, 2 * n3 * sizeof(float))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->sp_rays, rays, ray_bytes, hipMemcpyHostToDevice, c->stream));
+    const int rc = sparse_impl<kSrcRays>(c, p, c->sp_rays, n, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
+                                         c->stream, st);
+    if (rc != FRT_OK) return rc;
+    HIPCHK(c, hipMemcpy(out_rgb, c->sp_out, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIPCHK(c, hipMemcpy(out_var, c->sp_out + n3, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+
+extern "C" int frtx_camera_rays_device(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                                       float *rays_out, void *hip_stream)
+{
+    if (!c) return ray_err(c, FRT_E_INVALID, "camera_rays: null context");
+    if (!p || npix < 0 || npix > (int64_t)0xffffff00LL || p->nx <= 0 || p->ny <= 0 ||
+        (int64_t)p->nx * p->ny > (int64_t)INT32_MAX || p->sample_offset < 0)
+        return set_err(c, FRT_E_INVALID, "camera_rays: bad arguments");
+    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
+    if (npix == 0) return FRT_OK;
+    if (!pixels || !rays_out) return set_err(c, FRT_E_INVALID, "camera_rays: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    std::vector<int32_t> host((size_t)npix);
+    HIPCHK(c, hipMemcpyAsync(host.data(), pixels, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    const int64_t n = (int64_t)p->nx * p->ny;
+    for (int64_t i = 0; i < npix; ++i)
+        if (host[i] < 0 || host[i] >= n)
+            return set_err(c, FRT_E_INVALID, "camera_rays: entry " + std::to_string(i) + " is pixel " + std::to_string(host[i]) +
+                                                 ", outside [0, nx * ny)");
+    const dim3 grid((unsigned)((npix + 255) / 256)), block(256);
+    float4 *out = reinterpret_cast<float4 *>(rays_out);
+    if (p->flags & FRT_FLAG_SOBOL)
+        hipLaunchKernelGGL(film_reduce::camera_rays<kMatsSobol>, grid, block, 0, stream, c->S, pixels, (uint32_t)npix, p->nx, p->ny,
+                           p->seed, (uint32_t)p->sample_offset, out);
+    else
+        hipLaunchKernelGGL(film_reduce::camera_rays<kMatsNone>, grid, block, 0, stream, c->S, pixels, (uint32_t)npix, p->nx, p->ny,
+                           p->seed, (uint32_t)p->sample_offset, out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(stream));
     return FRT_OK;
 }
 #endif  // part 0

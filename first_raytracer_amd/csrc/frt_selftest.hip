@@ -8,6 +8,7 @@
 
 #include "frt_ctx.hpp"
 #include "frt_flatten.hpp"
+#include "frt_rays.hpp"
 #include "frt_tree_passes.hpp"
 #include "host/envdist.hpp"
 
@@ -15,19 +16,24 @@ using namespace frt;
 
 constexpr int kSelftestStack = 8;   // small, so the host self-test exercises the overflow entries
 
-// the self-test's per-pixel loop in precision R (fp64: the binary tree or the list)
+// the self-test's per-pixel loop in precision R (fp64: the binary tree or the list); with `rays`
+// the entries are first rays (frtx_selftest_radiance_host: ray_begin in path_begin's place)
 template <typename R, int MATS = kMatsAll>
 static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_render_params *p, const int32_t *pixels,
-                            int npix, bool wide, std::vector<int> &stack, float *out_rgb, uint64_t cnt[3])
+                            int npix, bool wide, std::vector<int> &stack, float *out_rgb, uint64_t cnt[3],
+                            const float *rays = nullptr)
 {
     uint32_t n_ext = 0, n_sh = 0;
     for (int i = 0; i < npix; ++i) {
-        const int pix = pixels[i];
+        const int pix = rays ? 0 : pixels[i];
         const int px = pix % p->nx, py = pix / p->nx;
+        float4 ray[2];
+        if (rays) memcpy(ray, rays + 8 * (size_t)i, sizeof(ray));
         V3<R> acc = zero3<R>();
         for (int smp = 0; smp < p->spp; ++smp) {
             PathState<R> P;
-            path_begin<MATS>(P, S, px, py, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)(smp + p->sample_offset));
+            if (rays) ray_begin<MATS>(P, ray[0], ray[1], p->seed, (uint32_t)(smp + p->sample_offset));
+            else path_begin<MATS>(P, S, px, py, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)(smp + p->sample_offset));
             ++cnt[0];
             for (;;) {
                 Hit<R> h;
@@ -62,6 +68,11 @@ static void selftest_pixels(const DevScene &S, const FlatScene &F, const frt_ren
                 out_rgb[3 * i + 1] = depth_moment_floor(out_rgb[3 * i], out_rgb[3 * i + 1], out_rgb[3 * i + 2]);
             continue;
         }
+        if (rays) {   // the ray lists divide (sparse_reduce): exact where the sum is
+            const R n = (R)p->spp;
+            out_rgb[3 * i] = (float)(acc.x / n); out_rgb[3 * i + 1] = (float)(acc.y / n); out_rgb[3 * i + 2] = (float)(acc.z / n);
+            continue;
+        }
         const R k = R(1) / (R)p->spp;
         out_rgb[3 * i] = (float)(acc.x * k); out_rgb[3 * i + 1] = (float)(acc.y * k); out_rgb[3 * i + 2] = (float)(acc.z * k);
     }
@@ -77,12 +88,20 @@ extern "C" int frt_selftest_path_host(const frt_scene_view *sv, const frt_render
     return frt_selftest_path_host_env(sv, p, pixels, npix, nullptr, out_rgb, st);
 }
 // ... with an environment image (frt_set_env_image's validation and conversion; NULL = none)
+static int selftest_replay(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels, const float *rays,
+                           int npix, const frt_image *env, float *out_rgb, frt_stats *st);
 extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
                                           int npix, const frt_image *env, float *out_rgb, frt_stats *st)
 {
     if (!sv || !p || !pixels || !out_rgb || npix < 0 || p->spp <= 0 || p->nx <= 0 || p->ny <= 0) return FRT_E_INVALID;
     for (int i = 0; i < npix; ++i)
         if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
+    return selftest_replay(sv, p, pixels, nullptr, npix, env, out_rgb, st);
+}
+// the replay of a checked list: pixels, or (rays) first rays
+static int selftest_replay(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels, const float *rays,
+                           int npix, const frt_image *env, float *out_rgb, frt_stats *st)
+{
     if (p->integrator == FRT_INTEGRATOR_DENOISE) return FRT_E_INVALID;   // a filter over a frame: no per-pixel code
     if (p->integrator == FRT_INTEGRATOR_ERROR) return FRT_E_INVALID;     // a reduction of a context's chunk sums: no per-pixel code
     // albedo, depth: fp32 and the hash stream whatever the flags say, and no environment
@@ -126,8 +145,8 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
         constexpr int X = decltype(extra)::value;
         auto run = [&](auto mats) {
             constexpr int M = decltype(mats)::value;
-            if (f64) selftest_pixels<double, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
-            else selftest_pixels<float, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt);
+            if (f64) selftest_pixels<double, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt, rays);
+            else selftest_pixels<float, M | X>(S, F, p, pixels, npix, wide, stack, out_rgb, cnt, rays);
         };
         if (env_sampling) run(std::integral_constant<int, kEnvNee>{});
         else if (env) run(std::integral_constant<int, kEnvAll>{});
@@ -148,6 +167,56 @@ extern "C" int frt_selftest_path_host_env(const frt_scene_view *sv, const frt_re
     return FRT_OK;
 }
 
+// frtx_radiance_rays on the host: the request and the list refused as the entry point refuses
+// them (the text in frt_last_error(NULL)), then ray_begin and the replay's loop per entry
+extern "C" int frtx_selftest_radiance_host(const frt_scene_view *sv, const frt_render_params *p, const float *rays, int64_t n,
+                                           const frt_image *env, float *out_rgb, frt_stats *st)
+{
+    auto fail = [](int code, const std::string &m) { frt::null_ctx_err() = m; return code; };
+    if (!sv || !p || n < 0 || n > INT32_MAX || (n > 0 && (!rays || !out_rgb))) return fail(FRT_E_INVALID, "radiance_rays: bad arguments");
+    const int k = p->integrator;
+    if (k == FRT_INTEGRATOR_NORMALS || k == FRT_INTEGRATOR_ALBEDO || k == FRT_INTEGRATOR_DEPTH)
+        return fail(FRT_E_UNSUPPORTED, "radiance_rays: path and ao only (normals, albedo and depth have no sparse kernel)");
+    if (k != FRT_INTEGRATOR_PATH && k != FRT_INTEGRATOR_AO)
+        return fail(FRT_E_INVALID, "radiance_rays: path and ao only (pssmlt is no per-pixel estimator; denoise and error are "
+                                   "films of a whole frame)");
+    if (p->shard_count != 1) return fail(FRT_E_INVALID, "radiance_rays: shard_count must be 1 (split the list instead)");
+    if (p->spp <= 0 || p->sample_offset < 0) return fail(FRT_E_INVALID, "bad render params");
+    std::string why;
+    if (frt::rays_first_bad(rays, n, why) >= 0) return fail(FRT_E_INVALID, "radiance_rays: " + why);
+    if (st) memset(st, 0, sizeof(*st));
+    if (n == 0) return FRT_OK;
+    frt_render_params q = *p;
+    q.nx = q.ny = 1;   // ignored
+    return selftest_replay(sv, &q, nullptr, rays, (int)n, env, out_rgb, st);
+}
+
+// frtx_camera_rays_device on the host: path_begin<MATS, float> over the scene flattened as an upload flattens it
+extern "C" int frtx_selftest_camera_rays_host(const frt_scene_view *sv, const frt_render_params *p, const int32_t *pixels,
+                                              int64_t npix, float *rays_out)
+{
+    if (!sv || !p || npix < 0 || (npix > 0 && (!pixels || !rays_out)) || p->nx <= 0 || p->ny <= 0 || p->sample_offset < 0 ||
+        (int64_t)p->nx * p->ny > (int64_t)INT32_MAX)
+        return FRT_E_INVALID;
+    for (int64_t i = 0; i < npix; ++i)
+        if (pixels[i] < 0 || pixels[i] >= p->nx * p->ny) return FRT_E_INVALID;
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false);
+    if (rc != FRT_OK) return rc;
+    const DevScene S = host_scene(F);
+    for (int64_t i = 0; i < npix; ++i) {
+        const int pix = pixels[i];
+        PathState<float> P;
+        if (p->flags & FRT_FLAG_SOBOL)
+            path_begin<kMatsSobol>(P, S, pix % p->nx, pix / p->nx, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)p->sample_offset);
+        else
+            path_begin<kMatsNone>(P, S, pix % p->nx, pix / p->nx, p->nx, p->ny, p->seed, (uint32_t)pix, (uint32_t)p->sample_offset);
+        const float rec[8] = {P.ro.x, P.ro.y, P.ro.z, P.rtmax, P.rd.x, P.rd.y, P.rd.z, i2f(pix)};
+        memcpy(rays_out + 8 * i, rec, sizeof(rec));
+    }
+    return FRT_OK;
+}
 
 // Self-test hook: n PSS-MLT bootstrap eye paths (fresh primary samples from the
 // bootstrap stream) through frt_mlt.hpp on the host; out6[i] = x, y, r, g, b, sc.

@@ -7,6 +7,7 @@
 //              [--denoise [--denoise-spp 16]]
 //              [--error-out v.pfm] [--target-error E --max-spp N [--first-spp 16] [--adaptive [--switch S]]]
 //              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
+//              [--camera latlong [--cam-origin x,y,z] [--cam-passes K]]
 //
 // --integrator pssmlt: renderer<pssmlt_gpu>, --ns = mutations per pixel.
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
@@ -27,6 +28,12 @@
 //   frt::kAdaptiveFirstSpp there; one line per pass with the
 //   samples over the frame, the pixels sampled and how; --counts-out writes the samples per pixel as
 //   PFM.  Not with --sobol.
+// --camera latlong: instead of the scene camera's frame, a lat-long light probe from that camera's
+//   origin, or from --cam-origin (frtx_radiance_rays over frt::latlong_rays, on the first GPU; path or ao): --res texels,
+//   --ns samples a texel and pass, written upright -- the +y pole is the top row as viewed -- so the
+//   image read back row by row from the top is an environment image for --env-map's convention.
+//   --cam-passes K: K passes at sample offsets k * ns, each through another point of the texels
+//   (hashed from the seed and k; one pass: the centres), averaged by frt_film_accumulate's rule.
 // --env: constant environment colour (the reference scenes' is black).
 // --env-map: a Radiance .hdr lat-long image as the environment (Scene::env_map over an
 //   image_texture, material.h:206-244); exclusive with --env.
@@ -64,7 +71,10 @@ int main(int argc, char **argv)
     int first_spp = 16;
     bool has_target = false, has_max_spp = false, has_first_spp = false, adaptive = false;
     double switch_share = frt::kAdaptiveSwitch;
-    std::string counts_out;
+    std::string counts_out, camera;
+    int cam_passes = 1;
+    double cam_origin[3] = {0, 0, 0};
+    bool has_cam_origin = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -99,6 +109,12 @@ int main(int argc, char **argv)
         else if (a == "--adaptive") adaptive = true;
         else if (a == "--switch") switch_share = std::atof(next());
         else if (a == "--counts-out") counts_out = next();
+        else if (a == "--camera") camera = next();
+        else if (a == "--cam-passes") cam_passes = std::atoi(next());
+        else if (a == "--cam-origin") {
+            if (std::sscanf(next(), "%lf,%lf,%lf", &cam_origin[0], &cam_origin[1], &cam_origin[2]) != 3) return 2;
+            has_cam_origin = true;
+        }
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -139,6 +155,13 @@ int main(int argc, char **argv)
     }
     if (until && max_spp <= 0) { std::fprintf(stderr, "--target-error needs --max-spp\n"); return 2; }
     if (until && denoise) { std::fprintf(stderr, "--target-error and --denoise exclude each other\n"); return 2; }
+    if (!camera.empty() && camera != "latlong") { std::fprintf(stderr, "unknown --camera %s (latlong)\n", camera.c_str()); return 2; }
+    if (camera.empty() && (cam_passes != 1 || has_cam_origin)) { std::fprintf(stderr, "--cam-passes / --cam-origin go with --camera\n"); return 2; }
+    if (!camera.empty() && (cam_passes < 1 || (integrator != "path" && integrator != "ao") || until || denoise || !error_out.empty())) {
+        std::fprintf(stderr, "--camera: a path or ao render of --ns samples and --cam-passes >= 1 passes "
+                             "(not with --target-error, --error-out or --denoise)\n");
+        return 2;
+    }
     try {
         if (until) std::printf("Resolution: %dx%d\nRendering until e <= %g, at most %ld samples\n", nx, ny, target_error, max_spp);
         else std::printf("Resolution: %dx%d\nSetting number of samples to %ld\n", nx, ny, ns);
@@ -194,7 +217,44 @@ int main(int argc, char **argv)
                 report_error(std::vector<float>(film.fout_image.begin(), film.fout_image.end()));
             }
         };
-        if (integrator == "pssmlt") {
+        if (!camera.empty()) {   // a lat-long probe from the camera's origin, through frtx_radiance_rays
+            frt_render_params p{};
+            if (integrator == "path") {
+                frt::renderer<frt::path_gpu> render;
+                render.seed = seed; render.env_sampling = env_sampling; render.roulette = roulette; render.sobol = sobol;
+                p = render.params(nx, ny, (int)ns);
+            } else {
+                frt::renderer<frt::ao_gpu> render;
+                render.seed = seed;
+                p = render.params(nx, ny, (int)ns);
+            }
+            const frt_scene_view view = s.view();
+            frt::device_set gpu({0}, view, s.env_map());
+            if (!has_cam_origin) std::memcpy(cam_origin, view.cam_origin, sizeof(cam_origin));
+            const size_t n = (size_t)nx * ny;
+            std::vector<float> acc(n * 3), pass(n * 3);
+            double ms = 0.0;
+            unsigned long long rays = 0;
+            for (int k = 0; k < cam_passes; ++k) {
+                double jx = 0.5, jy = 0.5;
+                if (cam_passes > 1) {   // a point of the texel hashed from (seed, k)
+                    uint64_t h = ((uint64_t)seed << 32 | (uint32_t)k) + 0x9E3779B97F4A7C15ull;
+                    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull; h = (h ^ (h >> 27)) * 0x94D049BB133111EBull; h ^= h >> 31;
+                    jx = (double)(h >> 40) / (double)(1 << 24); jy = (double)((h >> 8) & 0xffffff) / (double)(1 << 24);
+                }
+                const std::vector<float> list = frt::latlong_rays(cam_origin, nx, ny, jx, jy);
+                p.sample_offset = (int)(k * ns);
+                const frt_stats st = frt::radiance_rays(gpu.data()[0], p, list.data(), (int64_t)n, k ? pass.data() : acc.data());
+                if (k) frt::check(frt_film_accumulate(acc.data(), (int64_t)k * ns, pass.data(), ns, (int64_t)acc.size()), "frt_film_accumulate");
+                ms += st.kernel_ms;
+                rays += st.camera_rays + st.extension_rays + st.shadow_rays;
+            }
+            std::vector<float> up(n * 3);   // the film's row 0 is the bottom one: the probe's row 0 (+y) goes on top
+            for (int r = 0; r < ny; ++r) std::memcpy(&up[(size_t)(ny - 1 - r) * nx * 3], &acc[(size_t)r * nx * 3], (size_t)nx * 3 * sizeof(float));
+            film.store_film(up.data());
+            std::printf("Lat-long probe from (%g, %g, %g): %d passes of %ld samples, %llu rays, %.3f ms on the GPU\n", cam_origin[0],
+                        cam_origin[1], cam_origin[2], cam_passes, ns, rays, ms);
+        } else if (integrator == "pssmlt") {
             frt::renderer<frt::pssmlt_gpu> render;
             render.chains = chains;
             run(render);

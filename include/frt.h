@@ -705,6 +705,57 @@ int frtx_render_pixels(frt_ctx *ctx, const frt_render_params *p, const int32_t *
                        float *out_rgb, float *out_var, frt_stats *st);
 int frtx_render_pixels_device(frt_ctx *ctx, const frt_render_params *p, const int32_t *pixels, int64_t npix,
                               float *out_rgb, float *out_var, void *hip_stream, frt_stats *st);
+/* Radiance along caller-supplied first rays (not in the reference): this library's integrator --
+ * NEE + MIS, every material, the environment and its sampling, roulette, Sobol' points, fp64 --
+ * behind a first ray of the caller's instead of the thin-lens camera's: other cameras, light
+ * probes, baking at surface points, non-raster sampling.  frt_trace_device is the counterpart for
+ * callers with an integrator of their own.
+ * The ray record is frt_trace_device's, 8 floats: words 0-2 the origin, word 3 t_max of the first
+ * segment, words 4-6 the direction (any length, as the camera's), word 7 the entry's RNG stream id
+ * as uint32 bits -- it is never read as a float.  out_rgb[3i .. 3i + 2] is the mean of Li along ray
+ * i over samples [sample_offset, sample_offset + spp); every sample traces the same first ray.
+ * Sample s of entry i draws from the stream keyed (seed, stream id, s) as a pixel render keys
+ * (seed, pixel, s) (with FRT_FLAG_SOBOL: that sampler's key); dimensions 0-3 (film, lens) are not
+ * read, every bounce reads the dimensions it reads in a render.  ENTRIES WITH EQUAL STREAM IDS SHARE
+ * THEIR RANDOM NUMBERS: give independent estimates distinct ids (0 .. n - 1, say), and pass the
+ * same id to correlate on purpose.  The first ray is a camera ray in every respect: depth 0, a
+ * light it hits adds its full one-sided emission (no MIS), a miss -- or a first segment cut short
+ * by t_max -- adds the environment.  The mean is sum / spp, correctly rounded.
+ * out_var (NULL to skip): frtx_render_pixels' V under its chunk rule (samples_per_item, 0 =
+ * max(1, spp / 16)); with out_var and fewer than 2 chunks the call is FRT_E_INVALID.
+ * Integrators, precision and flags as in frtx_render_pixels (path and ao; _FP64 / _FP32,
+ * _ENV_SAMPLING, _ROULETTE, _SOBOL, _BVH2; the other plan flags do nothing); nx, ny and tile_size
+ * are ignored; shard_count must be 1.  Input domain, checked on the host before any kernel runs
+ * (the device variant reads the list back first): origins and directions finite, the direction
+ * not zero, t_max finite and > 0, |origin| < 1e8 (frt_trace_device's domain); a bad entry is
+ * FRT_E_INVALID with its index in the text.  n = 0 returns FRT_OK and writes nothing.  The call
+ * uses the pixel list's buffers, not the render's chunk sums: a FRT_INTEGRATOR_ERROR call after it
+ * still describes the last frt_render.  st: as frtx_render_pixels, camera_rays = samples = n spp,
+ * pixels = n.  A refusal made before the context is looked at is also kept, per thread, as the
+ * text of frt_last_error(NULL).
+ * frtx_radiance_rays: list and outputs in host memory.  frtx_radiance_rays_device: all three in
+ * device memory, launched on hip_stream (NULL: the context's); returns when the work is done. */
+int frtx_radiance_rays(frt_ctx *ctx, const frt_render_params *p, const float *rays, int64_t n,
+                       float *out_rgb, float *out_var, frt_stats *st);
+int frtx_radiance_rays_device(frt_ctx *ctx, const frt_render_params *p, const float *rays, int64_t n,
+                              float *out_rgb, float *out_var, void *hip_stream, frt_stats *st);
+/* The scene camera's own first rays as such records, to start from and perturb: entry i is the ray
+ * a render makes for pixel pixels[i] of the nx x ny frame at sample p->sample_offset (the film and
+ * lens points of seed, pixel and that sample; FRT_FLAG_SOBOL selects that sampler), always in fp32;
+ * word 3 is the kernels' t_max (FLT_MAX), word 7 the pixel.  frtx_radiance_rays of these records
+ * at spp = 1 and the same sample_offset is frtx_render_pixels of the pixels, bit for bit, where
+ * the render is fp32.  pixels and rays_out (npix x 8 floats) are device memory; the list is
+ * validated as frtx_render_pixels validates it.  Returns when the work is done. */
+int frtx_camera_rays_device(frt_ctx *ctx, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                            float *rays_out, void *hip_stream);
+/* The two calls through the same per-lane code on the host (host memory; the scene flattened as
+ * an upload flattens it, the material sets collapsed as frt_selftest_path_host_env collapses
+ * them; env: an environment image or NULL; FRT_FLAG_FP64 selects fp64).  The radiance hook
+ * refuses what frtx_radiance_rays refuses, with the text in frt_last_error(NULL). */
+int frtx_selftest_radiance_host(const frt_scene_view *scene, const frt_render_params *p, const float *rays, int64_t n,
+                                const frt_image *env, float *out_rgb, frt_stats *st);
+int frtx_selftest_camera_rays_host(const frt_scene_view *scene, const frt_render_params *p, const int32_t *pixels,
+                                   int64_t npix, float *rays_out);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <stdexcept>
@@ -394,6 +395,44 @@ inline frt_stats render_pixels(frt_ctx *ctx, const frt_render_params &p, const s
     check(frtx_render_pixels(ctx, &p, pixels.data(), (int64_t)pixels.size(), rgb.data(), variance ? variance->data() : nullptr, &st),
           "frtx_render_pixels", ctx);
     return st;
+}
+
+// frtx_radiance_rays (frt.h) on one context: the mean radiance along each of the n first rays
+// (records of 8 floats: origin, t_max, direction, RNG stream id as uint32 bits; host memory) through
+// the library's path or ao integrator, and with `var` their V.  rgb, var: n x 3 floats.
+inline frt_stats radiance_rays(frt_ctx *ctx, const frt_render_params &p, const float *rays, int64_t n, float *rgb,
+                               float *var = nullptr)
+{
+    frt_stats st{};
+    check(frtx_radiance_rays(ctx, &p, rays, n, rgb, var, &st), "frtx_radiance_rays", ctx);
+    return st;
+}
+// frtx_camera_rays_device (frt.h): the scene camera's first rays of the listed pixels at sample
+// p.sample_offset, as records for radiance_rays.  pixels and rays_out (npix x 8 floats) are device
+// memory; hip_stream NULL: the context's.
+inline void camera_rays(frt_ctx *ctx, const frt_render_params &p, const int32_t *pixels, int64_t npix, float *rays_out,
+                        void *hip_stream = nullptr)
+{
+    check(frtx_camera_rays_device(ctx, &p, pixels, npix, rays_out, hip_stream), "frtx_camera_rays_device", ctx);
+}
+// Ray records of a lat-long probe around `origin` in the environment image's convention
+// (frt_set_env_image: phi = atan2(d.x, -d.z), theta = acos(d.y), row 0 = the +y pole), nx x ny texels
+// in row-major order, each ray through (jx, jy) in [0, 1)^2 of its texel (0.5, 0.5: the centre);
+// streams 0 .. nx ny - 1.  The binding's cameras.latlong.
+inline std::vector<float> latlong_rays(const double origin[3], int nx, int ny, double jx = 0.5, double jy = 0.5)
+{
+    std::vector<float> rays((size_t)nx * ny * 8);
+    const double pi = 3.14159265358979323846;
+    for (int r = 0; r < ny; ++r)
+        for (int c = 0; c < nx; ++c) {
+            const double phi = 2.0 * pi * (c + jx) / nx, theta = pi * (r + jy) / ny, st = std::sin(theta);
+            const uint32_t id = (uint32_t)(r * nx + c);
+            float *q = &rays[8 * (size_t)id];
+            q[0] = (float)origin[0]; q[1] = (float)origin[1]; q[2] = (float)origin[2]; q[3] = 3.40282347e+38f;
+            q[4] = (float)(st * std::sin(phi)); q[5] = (float)std::cos(theta); q[6] = (float)(-st * std::cos(phi));
+            std::memcpy(&q[7], &id, sizeof(id));
+        }
+    return rays;
 }
 
 // The active share of the frame below which an adaptive pass goes through frtx_render_pixels: the
