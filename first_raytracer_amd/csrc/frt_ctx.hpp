@@ -4,10 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
 #include "frt.h"
+#include "frt_devbuf.hpp"
 #include "frt_kernels.hpp"
 
 struct ncclComm;   // rccl's communicator; only frt_multi.hip includes rccl.h
@@ -53,31 +55,28 @@ struct frt_ctx {
         int spi = 0, n_chunks = 0;
         uint32_t n_slots = 0;
     } last_render;
-    // workspace
-    float *partial = nullptr; size_t partial_bytes = 0;
+    // workspace: grow-only device buffers (frt_devbuf.hpp), each on the list that frt_destroy frees
+    std::vector<DevBufAny *> bufs;
+    DevBuf<float> partial{bufs}, slots_out{bufs};
     unsigned *counter = nullptr;
-    unsigned long long *wave_rays = nullptr; size_t wave_rays_n = 0;
-    float *slots_out = nullptr; size_t slots_out_bytes = 0;
-    unsigned long long *splat = nullptr; size_t splat_bytes = 0;   // PSS-MLT fixed-point splat film
+    DevBuf<unsigned long long> wave_rays{bufs}, splat{bufs};   // splat: the PSS-MLT fixed-point film
     // FRT_INTEGRATOR_DENOISE: the three feature films in slot order, and the pixel-order planes
     // of the filter (the packed guides and the two iterates, frt_denoise.hip)
-    float *dn_feat = nullptr; size_t dn_feat_bytes = 0;
-    float4 *dn_planes = nullptr; size_t dn_planes_bytes = 0;
+    DevBuf<float> dn_feat{bufs};
+    DevBuf<float4> dn_planes{bufs};
     // frt_render_multi on this context as shard 0: RCCL communicators over the
     // member devices (one per member, cached while the device list is the
     // same), the gather buffer and the device film
     std::vector<int> comm_devs;
     std::vector<ncclComm *> comms;   // ncclComm_t (frt_multi.hip)
-    float *gather = nullptr; size_t gather_bytes = 0;
-    float *film_dev = nullptr; size_t film_dev_bytes = 0;
+    DevBuf<float> gather{bufs}, film_dev{bufs};
     // frtx_render_pixels (frt_render_sparse.hip): buffers of its own -- the chunk sums, the
     // per-wave ray counters, and the host call's device copies of the list and the outputs --
     // so that `partial` and last_render still describe the last full render
-    float *sp_partial = nullptr; size_t sp_partial_bytes = 0;
-    unsigned long long *sp_wave_rays = nullptr; size_t sp_wave_rays_bytes = 0;
-    int32_t *sp_pixels = nullptr; size_t sp_pixels_bytes = 0;
-    float *sp_out = nullptr; size_t sp_out_bytes = 0;
-    float *sp_rays = nullptr; size_t sp_rays_bytes = 0;   // frtx_radiance_rays: the host call's device copy of its list
+    DevBuf<float> sp_partial{bufs}, sp_out{bufs};
+    DevBuf<unsigned long long> sp_wave_rays{bufs};
+    DevBuf<int32_t> sp_pixels{bufs};
+    DevBuf<float> sp_rays{bufs};   // frtx_radiance_rays: the host call's device copy of its list
 };
 
 #pragma GCC visibility push(hidden)
@@ -128,6 +127,32 @@ int trav_min(bool lds_scene, bool path = false);
 int min_desc(bool lds_scene);
 bool use_f64(const frt_ctx *c, const frt_render_params *p);
 int env_tables(frt_ctx *c);
+// What a path / AO render (a frame or a list) settles before it picks its plan: the sampling tables
+// of FRT_FLAG_ENV_SAMPLING (*env_sampling: the kernels that sample the image), the refusal of AO
+// over metal, and *f64 with the refusal of fp64 kernels for a scene uploaded without fp64 records
+int render_preamble(frt_ctx *c, const frt_render_params *p, bool *env_sampling, bool *f64);
+// One launch of a persistent kernel (path, PSS-MLT, the lists, the ray queries), in this order:
+// persist_plan, queue_headroom, persist_launch, the caller's follow-up kernels and its
+// hipEventRecord(c->ev1) where its kernel_ms ends, persist_finish, fill_plan_stats.
+struct Launcher;   // frt_plans.hpp
+struct Persist {
+    std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();   // of total_ms
+    int grid = 0;
+    size_t n_waves = 0;
+    bool diag = false;   // FRT_DIAG builds: the launch fills the per-phase counters (frt_diag_read)
+};
+// grid: the blocks of fn that the device holds at once, max_blocks at the most; counters, where the
+// kernel keeps per-wave ray counters: room for [n_waves][4]
+int persist_plan(frt_ctx *c, const void *fn, size_t lds, int64_t max_blocks, DevBuf<unsigned long long> *counters, Persist &P);
+// the 32-bit queue head runs past n_items by up to per_wave for each wave: refused with `msg`
+int queue_headroom(frt_ctx *c, const Persist &P, uint64_t n_items, uint64_t per_wave, const std::string &msg);
+// zero the queue (queue_bytes from `queue`), record ev0, launch (run = false: no work, no launch)
+int persist_launch(frt_ctx *c, const Persist &P, const char *name, const void *fn, size_t lds, void **args, unsigned *queue,
+                   size_t queue_bytes, hipStream_t st, bool run = true);
+// copy the counters (NULL: none were written), wait for the stream; *stats (may be NULL) is zeroed
+// and gets the counters' sums over the waves, kernel_ms = ev0 .. ev1 and total_ms, then the plan's fields
+int persist_finish(frt_ctx *c, const Persist &P, const unsigned long long *counters, hipStream_t st, frt_stats *stats);
+void fill_plan_stats(frt_stats *stats, const frt_ctx *c, const Launcher &L);
 // frt_multi.hip
 void free_comms(frt_ctx *c);
 // frt_denoise.hip: the filter of FRT_INTEGRATOR_DENOISE over a whole frame in slot order (shard 0

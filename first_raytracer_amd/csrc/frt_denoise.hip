@@ -109,14 +109,7 @@ int frt_denoise::run(frt_ctx *c, const frt_render_params *p, float *colour_slots
 {
     const int T = eff_tile(p), ntx = (p->nx + T - 1) / T;
     const size_t npix = (size_t)p->nx * p->ny;
-    const size_t bytes = 3 * npix * sizeof(float4);
-    if (bytes > c->dn_planes_bytes) {
-        if (c->dn_planes) HIPCHK(c, hipFree(c->dn_planes));
-        c->dn_planes = nullptr;
-        c->dn_planes_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dn_planes, bytes));
-        c->dn_planes_bytes = bytes;
-    }
+    if (const int rc = c->dn_planes.reserve(c, 3 * npix * sizeof(float4))) return rc;
     float4 *guides = c->dn_planes, *a = guides + npix, *b = a + npix;
     const int nbx = (p->nx + kDnBx - 1) / kDnBx, nby = (p->ny + kDnBy - 1) / kDnBy;
     const uint64_t blocks = (uint64_t)nbx * nby;

@@ -83,7 +83,7 @@ int frt_error::run(frt_ctx *c, const frt_render_params *p, float *out_slots, uin
     const int T = eff_tile(p), ntx = (p->nx + T - 1) / T;
     *ms = 0.0f;
     if (n_slots == 0) return FRT_OK;
-    if ((n_slots & 3u) != 0 || n_chunks < 2 || (size_t)n_chunks * n_slots * 3 * sizeof(float) > c->partial_bytes)
+    if ((n_slots & 3u) != 0 || n_chunks < 2 || (size_t)n_chunks * n_slots * 3 * sizeof(float) > c->partial.bytes)
         return set_err(c, FRT_E_INVALID, "error film: the recorded chunk sums do not fit the context's buffer");
     const uint64_t n_vec = 3ull * n_slots / 4;
     const int out_vec = (reinterpret_cast<uintptr_t>(out_slots) & 15u) == 0 ? 1 : 0;

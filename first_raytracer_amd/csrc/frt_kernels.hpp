@@ -186,6 +186,7 @@ template <class Scene> size_t lds_rest(const Scene &F) { return F.tris.size() + 
 
 // R: float (the product kernels) or double (the fp64 kernels, DESIGN.md
 // "Precision": list worlds under FRT_PRECISION_AUTO, every plan under _FP64)
+// sparse_kernel (frt_render_sparse.hip) holds a copy of this loop: a change here goes there too (DESIGN.md "One device loop")
 template <int STACK, int WORLD, bool LDS_SCENE, int WAVES = 1, int MATS = kMatsNone,
           int KIND = FRT_INTEGRATOR_PATH, typename R = float>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES))) void path_megakernel(

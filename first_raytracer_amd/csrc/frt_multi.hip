@@ -43,18 +43,6 @@ void free_comms(frt_ctx *c)
     c->comm_devs.clear();
 }
 
-// device buffer of at least `bytes` (grown, never shrunk)
-static int ensure_buf(frt_ctx *c, float **buf, size_t *have, size_t bytes)
-{
-    if (bytes <= *have) return FRT_OK;
-    if (*buf) HIPCHK(c, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIPCHK(c, hipMalloc(buf, bytes));
-    *have = bytes;
-    return FRT_OK;
-}
-
 #define NCCLCHK(ctx, x)                                                                            \
     do {                                                                                           \
         ncclResult_t r_ = (x);                                                                     \
@@ -113,9 +101,7 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
     const size_t shard_floats = (size_t)max_slots * 3;
     for (int i = 0; i < n; ++i) {
         HIPCHK(ctxs[i], hipSetDevice(ctxs[i]->device));
-        const int rc = ensure_buf(ctxs[i], &ctxs[i]->slots_out, &ctxs[i]->slots_out_bytes,
-                                  std::max<size_t>(shard_floats * sizeof(float), 16));
-        if (rc != FRT_OK) return rc;
+        if (const int rc = ctxs[i]->slots_out.reserve(ctxs[i], shard_floats * sizeof(float))) return rc;
     }
     std::vector<frt_stats> sts(n);
     std::vector<int> rcs(n, FRT_OK);
@@ -142,9 +128,8 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
         for (int j = 0; j < i; ++j) distinct &= devs[j] != devs[i];
     }
     HIPCHK(c0, hipSetDevice(c0->device));
-    int rc = ensure_buf(c0, &c0->gather, &c0->gather_bytes, std::max<size_t>((size_t)n * shard_floats * sizeof(float), 16));
-    if (rc == FRT_OK) rc = ensure_buf(c0, &c0->film_dev, &c0->film_dev_bytes, std::max<size_t>(film_n * sizeof(float), 16));
-    if (rc != FRT_OK) return rc;
+    if (const int rc = c0->gather.reserve(c0, (size_t)n * shard_floats * sizeof(float))) return rc;
+    if (const int rc = c0->film_dev.reserve(c0, film_n * sizeof(float))) return rc;
     if (distinct) {
         if (c0->comm_devs != devs) {
             free_comms(c0);
@@ -178,7 +163,7 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
             HIPCHK(c0, hipMemsetAsync(c0->film_dev, 0, film_n * sizeof(float), c0->stream));
             for (int i = 0; i < n; ++i) {
                 hipLaunchKernelGGL(film_add, dim3((unsigned)((film_n + 255) / 256)), dim3(256), 0, c0->stream,
-                                   c0->film_dev, c0->gather + (size_t)i * shard_floats, film_n);
+                                   c0->film_dev.get(), c0->gather + (size_t)i * shard_floats, film_n);
                 HIPCHK(c0, hipGetLastError());
             }
         }
@@ -187,7 +172,7 @@ extern "C" int frt_render_multi(frt_ctx **ctxs, int n, const frt_render_params *
         const int T = eff_tile(p);
         const uint64_t total = (uint64_t)n * (uint64_t)max_slots;
         hipLaunchKernelGGL(scatter_shards, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c0->stream,
-                           c0->gather, c0->film_dev, (uint32_t)max_slots, n, T, (p->nx + T - 1) / T, p->nx, p->ny);
+                           c0->gather.get(), c0->film_dev.get(), (uint32_t)max_slots, n, T, (p->nx + T - 1) / T, p->nx, p->ny);
         HIPCHK(c0, hipGetLastError());
     }
     if (mlt) {

@@ -137,22 +137,10 @@ extern "C" int frt_destroy(frt_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     free_scene(c);
-    if (c->partial) (void)hipFree(c->partial);
     if (c->counter) (void)hipFree(c->counter);
-    if (c->wave_rays) (void)hipFree(c->wave_rays);
-    if (c->slots_out) (void)hipFree(c->slots_out);
-    if (c->splat) (void)hipFree(c->splat);
-    if (c->dn_feat) (void)hipFree(c->dn_feat);
-    if (c->dn_planes) (void)hipFree(c->dn_planes);
     if (c->env_texels) (void)hipFree(c->env_texels);
     free_comms(c);
-    if (c->gather) (void)hipFree(c->gather);
-    if (c->film_dev) (void)hipFree(c->film_dev);
-    if (c->sp_partial) (void)hipFree(c->sp_partial);
-    if (c->sp_wave_rays) (void)hipFree(c->sp_wave_rays);
-    if (c->sp_pixels) (void)hipFree(c->sp_pixels);
-    if (c->sp_out) (void)hipFree(c->sp_out);
-    if (c->sp_rays) (void)hipFree(c->sp_rays);
+    for (DevBufAny *b : c->bufs) b->release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -441,21 +429,29 @@ static int pick_launcher(const frt_ctx *c, int integrator, int flags, Launcher &
 }
 
 
-// ---- ray queries: trace_kernel plans (the path plans' residency rules) ----
-struct TraceLauncher {
-    const void *fn = nullptr;
-    size_t lds = 0;
-    int waves = 0;
-    bool lds_scene = false;
-    size_t scene_lds = 0;   // as Launcher::scene_lds
-    int stack = 0;          // per-lane stack entries of the plan (0: a list world has none)
-    bool wide = false;      // the 4-wide tree
-};
-template <int STACK, int WORLD, bool LDS, int WAVES>
-static TraceLauncher make_trace(size_t scene_bytes)
+int render_preamble(frt_ctx *c, const frt_render_params *p, bool *env_sampling, bool *f64)
 {
-    TraceLauncher L;
-    L.stack = WORLD != FRT_WORLD_LIST ? STACK : 0;
+    // FRT_FLAG_ENV_SAMPLING: path renders of a context with an image that has any luminance
+    *env_sampling = false;
+    if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator == FRT_INTEGRATOR_PATH && c->env_texels) {
+        if (const int trc = env_tables(c)) return trc;
+        *env_sampling = c->env_tab == frt_ctx::kEnvTabBuilt;
+    }
+    if (p->integrator == FRT_INTEGRATOR_AO && c->has_metal)   // ao::Li -> constant_pdf::generate throws (pdf.h:195-198)
+        return set_err(c, FRT_E_UNSUPPORTED, "ao integrator: metal has no sampling pdf (constant_pdf::generate)");
+    *f64 = use_f64(c, p);
+    if (*f64 && !c->has_f64)
+        return set_err(c, FRT_E_INVALID, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
+                                         "before frt_upload_scene");
+    return FRT_OK;
+}
+
+// ---- ray queries: trace_kernel plans (the path plans' residency rules) ----
+template <int STACK, int WORLD, bool LDS, int WAVES>
+static Launcher make_trace(size_t scene_bytes)
+{
+    Launcher L;
+    L.stack = WORLD != FRT_WORLD_LIST ? STACK : 0;   // a list world has none
     L.wide = WORLD == kWorldBvh4;
     L.fn = reinterpret_cast<const void *>(&trace_kernel<STACK, WORLD, LDS, WAVES>);
     L.lds = (WORLD != FRT_WORLD_LIST ? (size_t)STACK * kBlock * sizeof(int) : 0) + (LDS ? scene_bytes : 0);
@@ -466,7 +462,7 @@ static TraceLauncher make_trace(size_t scene_bytes)
 }
 // register cap of the ray-query kernel: FRT_TRACE_WAVES (6 / 8 / 10; A/B knob, not part of the C-ABI)
 template <int STACK, int WORLD, bool LDS>
-static TraceLauncher trace_waves(size_t sb)
+static Launcher trace_waves(size_t sb)
 {
     const char *e = std::getenv("FRT_TRACE_WAVES");
     const int w = e ? std::atoi(e) : 8;
@@ -474,7 +470,7 @@ static TraceLauncher trace_waves(size_t sb)
     if (w == 10) return make_trace<STACK, WORLD, LDS, 10>(sb);
     return make_trace<STACK, WORLD, LDS, 8>(sb);
 }
-static int pick_trace(const frt_ctx *c, int flags, TraceLauncher &L)
+static int pick_trace(const frt_ctx *c, int flags, Launcher &L)
 {
     return walk_plan(c, flags, [&](auto r, size_t scene_bytes) -> int {
         using R = decltype(r);
@@ -488,21 +484,18 @@ static int pick_trace(const frt_ctx *c, int flags, TraceLauncher &L)
 extern "C" int frt_trace_device(frt_ctx *c, const float *rays, int64_t n, float *hits, int flags, void *hip_stream,
                                 frt_stats *st)
 {
-    const auto t_start = std::chrono::steady_clock::now();
+    Persist P;
     if (!c || n < 0 || (n > 0 && (!rays || !hits))) return FRT_E_INVALID;
     if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    TraceLauncher L;
+    Launcher L;
     if (pick_trace(c, flags, L) != FRT_OK) return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, L.fn, kBlock, L.lds) != hipSuccess || bpc <= 0) bpc = 1;
-    const int64_t want = std::max<int64_t>(1, (n + kBlock - 1) / kBlock);
-    const int grid = (int)std::min<int64_t>((int64_t)c->n_cu * bpc, want);
-    // the 32-bit ray-queue head runs past n by up to one chunk per wave
-    // (render_impl has the same headroom check)
-    if (n + (int64_t)(grid * kBlock / 64) * kTraceChunk >= (int64_t)0xffffffffLL)
-        return set_err(c, FRT_E_UNSUPPORTED, "frt_trace_device: too many rays for one call (2^32 - 1 less the queue headroom)");
+    if (const int rc = persist_plan(c, L.fn, L.lds, std::max<int64_t>(1, (n + kBlock - 1) / kBlock), nullptr, P)) return rc;
+    // the ray-queue head runs past n by up to one chunk per wave
+    if (const int rc = queue_headroom(c, P, (uint64_t)n, kTraceChunk,
+                                      "frt_trace_device: too many rays for one call (2^32 - 1 less the queue headroom)"))
+        return rc;
     DevRays R{};
     R.ray = reinterpret_cast<const float4 *>(rays);
     R.hit = reinterpret_cast<float4 *>(hits);
@@ -511,29 +504,13 @@ extern "C" int frt_trace_device(frt_ctx *c, const float *rays, int64_t n, float 
     // its own queue word, a cache line away from the render queue's: a trace and
     // a render of one context on two streams do not share a queue head
     R.counter = c->counter + kTraceCounterWord;
-    HIPCHK(c, hipMemsetAsync(R.counter, 0, sizeof(unsigned), stream));
-    HIPCHK(c, hipEventRecord(c->ev0, stream));
-    if (n > 0) {
-        DevScene Sarg = c->S;
-        void *args[] = {&Sarg, &R};
-        const hipError_t le = hipLaunchKernel(L.fn, dim3(grid), dim3(kBlock), args, L.lds, stream);
-        if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("trace_kernel launch: ") + hipGetErrorString(le));
-    }
+    DevScene Sarg = c->S;
+    void *args[] = {&Sarg, &R};
+    if (const int rc = persist_launch(c, P, "trace_kernel", L.fn, L.lds, args, R.counter, sizeof(unsigned), stream, n > 0)) return rc;
     HIPCHK(c, hipEventRecord(c->ev1, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (st) {
-        memset(st, 0, sizeof(*st));
-        st->camera_rays = (uint64_t)n;
-        st->kernel_ms = ms;
-        st->scene_in_lds = L.lds_scene ? 1u : 0u;
-        st->waves_cap = (uint32_t)L.waves;
-        st->stack_entries = (uint32_t)L.stack;
-        st->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
-        st->scene_bytes = L.lds_scene ? L.scene_lds : c->scene_lds_bytes;   // what this plan reads
-        st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    }
+    if (const int rc = persist_finish(c, P, nullptr, stream, st)) return rc;   // the kernel keeps no ray counters
+    if (st) st->camera_rays = (uint64_t)n;
+    fill_plan_stats(st, c, L);
     return FRT_OK;
 }
 
@@ -573,6 +550,61 @@ extern "C" int frt_diag_read(unsigned long long *out)
 }
 #endif
 
+// ---- one launch of a persistent kernel (frt_ctx.hpp) ----
+int persist_plan(frt_ctx *c, const void *fn, size_t lds, int64_t max_blocks, DevBuf<unsigned long long> *counters, Persist &P)
+{
+    int bpc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kBlock, lds) != hipSuccess || bpc <= 0) bpc = 1;
+    P.grid = (int)std::min<int64_t>((int64_t)c->n_cu * bpc, max_blocks);
+    P.n_waves = (size_t)P.grid * kBlock / 64;
+    return counters ? counters->reserve(c, P.n_waves * 4 * sizeof(unsigned long long)) : FRT_OK;
+}
+int queue_headroom(frt_ctx *c, const Persist &P, uint64_t n_items, uint64_t per_wave, const std::string &msg)
+{
+    return n_items + (uint64_t)P.n_waves * per_wave >= 0xffffffffULL ? set_err(c, FRT_E_UNSUPPORTED, msg) : FRT_OK;
+}
+int persist_launch(frt_ctx *c, const Persist &P, const char *name, const void *fn, size_t lds, void **args, unsigned *queue,
+                   size_t queue_bytes, hipStream_t st, bool run)
+{
+    HIPCHK(c, hipMemsetAsync(queue, 0, queue_bytes, st));
+#if defined(FRT_DIAG)
+    if (const int drc = P.diag ? diag_begin(c, P.n_waves, st) : FRT_OK) return drc;
+#endif
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    const hipError_t le = run ? hipLaunchKernel(fn, dim3(P.grid), dim3(kBlock), args, lds, st) : hipSuccess;
+    return le == hipSuccess ? FRT_OK : set_err(c, FRT_E_HIP, std::string(name) + " launch: " + hipGetErrorString(le));
+}
+int persist_finish(frt_ctx *c, const Persist &P, const unsigned long long *counters, hipStream_t st, frt_stats *stats)
+{
+    std::vector<unsigned long long> wr(counters ? P.n_waves * 4 : 0);
+    if (counters) HIPCHK(c, hipMemcpyAsync(wr.data(), counters, wr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+#if defined(FRT_DIAG)
+    if (const int drc = P.diag ? diag_end(c, P.n_waves) : FRT_OK) return drc;
+#endif
+    if (!stats) return FRT_OK;
+    memset(stats, 0, sizeof(*stats));
+    for (size_t w = 0; w < wr.size(); w += 4) {
+        stats->camera_rays += wr[w]; stats->extension_rays += wr[w + 1];
+        stats->shadow_rays += wr[w + 2]; stats->samples += wr[w + 3];
+    }
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - P.t_start).count();
+    return FRT_OK;
+}
+void fill_plan_stats(frt_stats *stats, const frt_ctx *c, const Launcher &L)
+{
+    if (!stats) return;
+    stats->scene_in_lds = L.lds_scene ? 1u : 0u;
+    stats->waves_cap = (uint32_t)L.waves;
+    stats->stack_entries = (uint32_t)L.stack;
+    stats->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
+    stats->scene_bytes = L.lds_scene ? L.scene_lds : c->scene_lds_bytes;   // what this plan reads
+    stats->fp64 = L.f64 ? 1u : 0u;
+}
+
 // The PSS-MLT plan of a context: the bootstrap and chain kernels, the traversal stack and the
 // LDS bytes of the two launches.  No device call: frtx_selftest_plan asks it too.
 struct MltPlan {
@@ -611,13 +643,9 @@ static int pick_mlt(frt_ctx *c, int flags, MltPlan &P)
 
 static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, hipStream_t st, frt_stats *stats)
 {
-    const auto t_start = std::chrono::steady_clock::now();
+    Persist PL;
     MltPlan P;
     if (const int prc = pick_mlt(c, p->flags, P)) return prc;
-    const void *const kboot = P.boot, *const kchain = P.chain;
-    const int stack = P.stack;
-    const size_t lds_boot = P.lds_boot, lds = P.lds;
-    const bool lds_scene = P.lds_scene, oct = P.oct;
     const uint32_t n_chains = (uint32_t)p->mlt_chains;
     const uint32_t n_local = (n_chains > (uint32_t)p->shard_index)
                                  ? (n_chains - 1 - (uint32_t)p->shard_index) / (uint32_t)p->shard_count + 1 : 0;
@@ -627,12 +655,7 @@ static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, h
     // bootstrap normaliser (identical on every shard: same streams, fixed-order host sum)
     const int n_init = p->mlt_bootstrap;
     const size_t need = std::max<size_t>((size_t)n_init * sizeof(float), (size_t)kMltRow * n_local * sizeof(float));
-    if (need > c->partial_bytes) {
-        if (c->partial) HIPCHK(c, hipFree(c->partial));
-        c->partial = nullptr;
-        HIPCHK(c, hipMalloc(&c->partial, need));
-        c->partial_bytes = need;
-    }
+    if (const int rc = c->partial.reserve(c, need)) return rc;
 #if defined(FRT_DIAG)
     // the bootstrap's traversal ticks too: a diagnostic buffer for its grid (zeroed again before the chains)
     if (const int drc = diag_begin(c, (size_t)(n_init + kBlock - 1) / kBlock * (kBlock / 64), st)) return drc;
@@ -643,7 +666,7 @@ static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, h
         float *sc = c->partial;
         DevScene Sarg = c->S;
         void *args[] = {&Sarg, &nx, &ny, &seed, &ni, &sc};
-        HIPCHK(c, hipLaunchKernel(kboot, dim3((n_init + kBlock - 1) / kBlock), dim3(kBlock), args, lds_boot, st));
+        HIPCHK(c, hipLaunchKernel(P.boot, dim3((n_init + kBlock - 1) / kBlock), dim3(kBlock), args, P.lds_boot, st));
     }
     std::vector<float> sc(n_init);
     HIPCHK(c, hipMemcpyAsync(sc.data(), c->partial, n_init * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -651,16 +674,8 @@ static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, h
     double b = 0.0;
     for (float v : sc) b += v;
     b /= n_init;
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kchain, kBlock, lds) != hipSuccess || bpc <= 0) bpc = 1;
-    const int grid = std::max(1, std::min<int>(c->n_cu * bpc, (int)((n_local + kBlock - 1) / kBlock)));
-    const size_t n_waves = (size_t)grid * kBlock / 64;
-    if (n_waves > c->wave_rays_n) {
-        if (c->wave_rays) HIPCHK(c, hipFree(c->wave_rays));
-        c->wave_rays = nullptr;
-        HIPCHK(c, hipMalloc(&c->wave_rays, n_waves * 4 * sizeof(unsigned long long)));
-        c->wave_rays_n = n_waves;
-    }
+    if (const int rc = persist_plan(c, P.chain, P.lds, std::max<int64_t>(1, (n_local + kBlock - 1) / kBlock), &c->wave_rays, PL)) return rc;
+    PL.diag = true;
     MltWork W{};
     W.nx = p->nx; W.ny = p->ny; W.seed = p->seed;
     W.shard_index = p->shard_index; W.shard_count = p->shard_count;
@@ -670,56 +685,30 @@ static int render_mlt(frt_ctx *c, const frt_render_params *p, float *dev_film, h
     W.s2p = 0.1f;
     W.logp = (float)std::log((double)0.1f / (2.0 / (double)(p->nx + p->ny)));
     const size_t n_film = (size_t)p->nx * p->ny * 3;
-    if (n_film * sizeof(unsigned long long) > c->splat_bytes) {
-        if (c->splat) HIPCHK(c, hipFree(c->splat));
-        c->splat = nullptr;
-        HIPCHK(c, hipMalloc(&c->splat, n_film * sizeof(unsigned long long)));
-        c->splat_bytes = n_film * sizeof(unsigned long long);
-    }
+    if (const int rc = c->splat.reserve(c, n_film * sizeof(unsigned long long))) return rc;
     W.U = c->partial; W.film = c->splat; W.counter = c->counter; W.wave_rays = c->wave_rays;
-    W.trav_min = trav_min(lds_scene);
-    W.min_desc = min_desc(lds_scene);
+    W.trav_min = trav_min(P.lds_scene);
+    W.min_desc = min_desc(P.lds_scene);
     HIPCHK(c, hipMemsetAsync(c->splat, 0, n_film * sizeof(unsigned long long), st));
-    HIPCHK(c, hipMemsetAsync(c->counter, 0, 64, st));
-#if defined(FRT_DIAG)
-    if (const int drc = diag_begin(c, n_waves, st)) return drc;
-#endif
-    HIPCHK(c, hipEventRecord(c->ev0, st));
-    if (n_local > 0 && steps > 0) {
-        DevScene Sarg = c->S;
-        void *args[] = {&Sarg, &W};
-        HIPCHK(c, hipLaunchKernel(kchain, dim3(grid), dim3(kBlock), args, lds, st));
-    }
+    const bool run = n_local > 0 && steps > 0;
+    DevScene Sarg = c->S;
+    void *args[] = {&Sarg, &W};
+    if (const int rc = persist_launch(c, PL, "mlt_megakernel", P.chain, P.lds, args, c->counter, 64, st, run)) return rc;
     HIPCHK(c, hipEventRecord(c->ev1, st));
-    mlt_film_to_float<<<dim3((unsigned)((n_film + kBlock - 1) / kBlock)), dim3(kBlock), 0, st>>>(c->splat, dev_film, n_film);
+    mlt_film_to_float<<<dim3((unsigned)((n_film + kBlock - 1) / kBlock)), dim3(kBlock), 0, st>>>(c->splat.get(), dev_film, n_film);
     HIPCHK(c, hipGetLastError());
-    std::vector<unsigned long long> wr(n_waves * 4, 0);
-    if (n_local > 0 && steps > 0)
-        HIPCHK(c, hipMemcpyAsync(wr.data(), c->wave_rays, wr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-#if defined(FRT_DIAG)
-    if (const int drc = diag_end(c, n_waves)) return drc;
-#endif
+    if (const int rc = persist_finish(c, PL, run ? c->wave_rays.get() : nullptr, st, stats)) return rc;
     if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        for (size_t w = 0; w < n_waves; ++w) {
-            stats->camera_rays += wr[4 * w]; stats->extension_rays += wr[4 * w + 1];
-            stats->shadow_rays += wr[4 * w + 2]; stats->samples += wr[4 * w + 3];
-        }
         stats->pixels = (uint64_t)p->nx * p->ny;
         stats->work_items = n_local;
-        stats->scene_in_lds = lds_scene ? 1u : 0u;
-        stats->stack_entries = (uint32_t)stack;
+        stats->scene_in_lds = P.lds_scene ? 1u : 0u;
+        stats->stack_entries = (uint32_t)P.stack;
         stats->bvh_depth = (uint32_t)c->stack_needed;
         // the LDS copy the chain kernel loads (the octant node copies on that plan)
-        stats->scene_bytes = oct ? c->scene_lds_bytes_oct : c->scene_lds_bytes;
-        stats->kernel_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        stats->scene_bytes = P.oct ? c->scene_lds_bytes_oct : c->scene_lds_bytes;
     }
     c->last_mlt_b = b;
-    c->mlt_rows = (n_local > 0 && steps > 0) ? n_local : 0;
+    c->mlt_rows = run ? n_local : 0;
     return FRT_OK;
 }
 
@@ -808,14 +797,7 @@ static int render_denoise(frt_ctx *c, const frt_render_params *p, float *dev_slo
     if (n_slots64 >= 0xffffffffULL) return set_err(c, FRT_E_UNSUPPORTED, "frame too large for one call");
     const uint32_t n_slots = (uint32_t)n_slots64;
     const size_t plane = (size_t)n_slots * 3;
-    const size_t fbytes = std::max<size_t>(3 * plane * sizeof(float), 16);
-    if (fbytes > c->dn_feat_bytes) {
-        if (c->dn_feat) HIPCHK(c, hipFree(c->dn_feat));
-        c->dn_feat = nullptr;
-        c->dn_feat_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dn_feat, fbytes));
-        c->dn_feat_bytes = fbytes;
-    }
+    if (const int rc = c->dn_feat.reserve(c, 3 * plane * sizeof(float))) return rc;
     const int kinds[3] = {FRT_INTEGRATOR_NORMALS, FRT_INTEGRATOR_DEPTH, FRT_INTEGRATOR_ALBEDO};   // albedo last: its plan fields stay
     float *films[3] = {c->dn_feat, c->dn_feat + 2 * plane, c->dn_feat + plane};
     frt_stats sum{};
@@ -888,7 +870,7 @@ static int render_error(frt_ctx *c, const frt_render_params *p, float *dev_slots
 // render_impl proper; the wrapper below keeps c->last_render
 static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_slots, hipStream_t st, frt_stats *stats)
 {
-    const auto t_start = std::chrono::steady_clock::now();
+    Persist P;
     if (!params_ok(p)) {
         if (p->integrator == FRT_INTEGRATOR_DENOISE && p->shard_count != 1)
             return set_err(c, FRT_E_INVALID, "denoise: shard_count must be 1 (the filter's stencil crosses tiles); "
@@ -912,14 +894,8 @@ static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_s
                                              "(its primary-sample layout is the reference's); render without the flag");
         return render_mlt(c, p, dev_slots, st, stats);
     }
-    // FRT_FLAG_ENV_SAMPLING: path renders of a context with an image that has any luminance
-    bool env_sampling = false;
-    if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator == FRT_INTEGRATOR_PATH && c->env_texels) {
-        if (const int trc = env_tables(c)) return trc;
-        env_sampling = c->env_tab == frt_ctx::kEnvTabBuilt;
-    }
-    if (p->integrator == FRT_INTEGRATOR_AO && c->has_metal)   // ao::Li -> constant_pdf::generate throws (pdf.h:195-198)
-        return set_err(c, FRT_E_UNSUPPORTED, "ao integrator: metal has no sampling pdf (constant_pdf::generate)");
+    bool env_sampling = false, f64 = false;
+    if (const int rc = render_preamble(c, p, &env_sampling, &f64)) return rc;
     const int T = eff_tile(p);
     const int nmt = my_tiles(p);
     // 32-bit slot indices: params_ok caps the frame at 2^31 - 1 pixels, so a shard's padded
@@ -929,16 +905,11 @@ static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_s
     const uint32_t n_slots = (uint32_t)n_slots64;
     // kernel variant: stack depth, world kind, LDS-resident scene
     Launcher L;
-    const bool f64 = use_f64(c, p);
-    const int prc = pick_launcher(c, p->integrator, p->flags, L, f64, env_sampling);
-    if (prc == FRT_E_INVALID)
-        return set_err(c, prc, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
-                               "before frt_upload_scene");
-    if (prc != FRT_OK) return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, L.fn, kBlock, L.lds) != hipSuccess || bpc <= 0) bpc = 1;
-    const int grid = c->n_cu * bpc;
-    const long long lanes = (long long)grid * kBlock;
+    if (pick_launcher(c, p->integrator, p->flags, L, f64, env_sampling) != FRT_OK)
+        return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
+    if (const int rc = persist_plan(c, L.fn, L.lds, INT32_MAX, &c->wave_rays, P)) return rc;
+    P.diag = true;
+    const long long lanes = (long long)P.grid * kBlock;
     // the granule follows the whole frame's slots, not the shard's: every
     // shard cuts its pixels' samples into the same chunks, so the per-pixel
     // sums (and the film) are byte-identical for any shard count
@@ -951,23 +922,8 @@ static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_s
     const char *gb = std::getenv("FRT_GRAB");
     const uint32_t grab = (uint32_t)std::min(std::max(gb ? std::atoi(gb) : kQueueGrab, 1), 4096);
     // the counter runs past n_items by at most one grab per wave
-    if (n_items + (unsigned long long)(lanes / 64) * (grab + 64) >= 0xffffffffULL)
-        return set_err(c, FRT_E_UNSUPPORTED, "frame too large for one call: shard it");
-    // workspace
-    const size_t pbytes = std::max<size_t>((size_t)n_chunks * n_slots * 3 * sizeof(float), 16);
-    if (pbytes > c->partial_bytes) {
-        if (c->partial) HIPCHK(c, hipFree(c->partial));
-        c->partial = nullptr;
-        HIPCHK(c, hipMalloc(&c->partial, pbytes));
-        c->partial_bytes = pbytes;
-    }
-    const size_t n_waves = (size_t)grid * kBlock / 64;
-    if (n_waves > c->wave_rays_n) {
-        if (c->wave_rays) HIPCHK(c, hipFree(c->wave_rays));
-        c->wave_rays = nullptr;
-        HIPCHK(c, hipMalloc(&c->wave_rays, n_waves * 4 * sizeof(unsigned long long)));
-        c->wave_rays_n = n_waves;
-    }
+    if (const int rc = queue_headroom(c, P, n_items, grab + 64, "frame too large for one call: shard it")) return rc;
+    if (const int rc = c->partial.reserve(c, (size_t)n_chunks * n_slots * 3 * sizeof(float))) return rc;
     DevWork W{};
     W.nx = p->nx; W.ny = p->ny; W.spp = p->spp; W.max_depth = p->max_depth; W.seed = p->seed;
     W.s_off = (uint32_t)p->sample_offset;
@@ -978,51 +934,26 @@ static int render_impl_body(frt_ctx *c, const frt_render_params *p, float *dev_s
     W.trav_min = trav_min(L.lds_scene, p->integrator == FRT_INTEGRATOR_PATH);
     W.min_desc = min_desc(L.lds_scene);
 
-    HIPCHK(c, hipMemsetAsync(c->counter, 0, 64, st));
-#if defined(FRT_DIAG)
-    if (const int drc = diag_begin(c, n_waves, st)) return drc;
-#endif
-    HIPCHK(c, hipEventRecord(c->ev0, st));
     DevScene Sarg = c->S;
     void *args[] = {&Sarg, &W};
-    const hipError_t le = hipLaunchKernel(L.fn, dim3(grid), dim3(kBlock), args, L.lds, st);
-    if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("path_megakernel launch: ") + hipGetErrorString(le));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
+    if (const int rc = persist_launch(c, P, "path_megakernel", L.fn, L.lds, args, c->counter, 64, st)) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, st));   // kernel_ms: the render without its film reduction
     if (n_slots > 0) {
         if (p->integrator == FRT_INTEGRATOR_ALBEDO || p->integrator == FRT_INTEGRATOR_DEPTH)
-            hipLaunchKernelGGL(film_reduce_mean, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial, dev_slots,
+            hipLaunchKernelGGL(film_reduce_mean, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.get(), dev_slots,
                                n_slots, n_chunks, p->spp, T, W.ntx, p->shard_index, p->shard_count, p->nx, p->ny,
                                p->integrator == FRT_INTEGRATOR_DEPTH ? 1 : 0);
         else
-            hipLaunchKernelGGL(film_reduce, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial, dev_slots, n_slots,
+            hipLaunchKernelGGL(film_reduce, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.get(), dev_slots, n_slots,
                                n_chunks, p->spp, T, W.ntx, p->shard_index, p->shard_count, p->nx, p->ny);
         HIPCHK(c, hipGetLastError());
     }
-    std::vector<unsigned long long> wr(n_waves * 4);
-    HIPCHK(c, hipMemcpyAsync(wr.data(), c->wave_rays, wr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-#if defined(FRT_DIAG)
-    if (const int drc = diag_end(c, n_waves)) return drc;
-#endif
+    if (const int rc = persist_finish(c, P, c->wave_rays, st, stats)) return rc;
     if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        for (size_t w = 0; w < n_waves; ++w) {
-            stats->camera_rays += wr[4 * w]; stats->extension_rays += wr[4 * w + 1];
-            stats->shadow_rays += wr[4 * w + 2]; stats->samples += wr[4 * w + 3];
-        }
         stats->pixels = shard_pixels(p);
         stats->work_items = n_items;
-        stats->scene_in_lds = L.lds_scene ? 1u : 0u;
-        stats->waves_cap = (uint32_t)L.waves;
-        stats->stack_entries = (uint32_t)L.stack;
-        stats->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
-        stats->scene_bytes = L.lds_scene ? L.scene_lds : c->scene_lds_bytes;   // what this plan reads
-        stats->kernel_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        stats->fp64 = L.f64 ? 1u : 0u;
     }
+    fill_plan_stats(stats, c, L);
     // the chunk sums of this render stay in `partial`: FRT_INTEGRATOR_ERROR reduces them
     auto &r = c->last_render;
     r.nx = p->nx; r.ny = p->ny; r.spp = p->spp; r.tile = T; r.shard_index = p->shard_index; r.shard_count = p->shard_count;
@@ -1066,13 +997,7 @@ extern "C" int frt_render(frt_ctx *c, const frt_render_params *p, float *film_rg
     }
     const int64_t ns = frt_shard_slot_count(p);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = std::max<size_t>((size_t)ns * 3 * sizeof(float), 16);
-    if (bytes > c->slots_out_bytes) {
-        if (c->slots_out) HIPCHK(c, hipFree(c->slots_out));
-        c->slots_out = nullptr;
-        HIPCHK(c, hipMalloc(&c->slots_out, bytes));
-        c->slots_out_bytes = bytes;
-    }
+    if (const int rc = c->slots_out.reserve(c, (size_t)ns * 3 * sizeof(float))) return rc;
     std::vector<float> host((size_t)ns * 3);
     std::vector<int32_t> map((size_t)ns);
     if (denoise) {   // the colour, in slot order (padding slots: 0)
@@ -1119,7 +1044,7 @@ extern "C" int frtx_selftest_plan(const frt_plan_query *q, frt_plan_answer *a)
         return fn && dladdr(fn, &info) ? (uint64_t)((const char *)fn - (const char *)info.dli_fbase) : 0;
     };
     if (q->kind == 1) {
-        TraceLauncher L;
+        Launcher L;
         a->rc = pick_trace(&c, q->flags, L);
         a->lds = (int64_t)L.lds; a->waves = L.waves; a->lds_scene = L.lds_scene; a->scene_lds = (int64_t)L.scene_lds;
         a->kernel = handle(L.fn);

@@ -31,7 +31,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -50,31 +49,24 @@
 
 #pragma GCC visibility push(hidden)
 namespace frt_sparse {
-struct SparseLauncher {
-    const void *fn = nullptr;
-    size_t lds = 0;
-    int stack = 0;
-    bool wide = false, f64 = false;
-};
 // what a list's entries are: pixels of the frame (frtx_render_pixels) or first rays (frtx_radiance_rays)
 constexpr int kSrcPixels = 0, kSrcRays = 1;
 // the lambertian path kernels and the AO kernels (env: the context has an image)
-template <int SRC> int pick_base(const frt_ctx *c, int integrator, int flags, bool f64, bool env, SparseLauncher &L);   // piece 0
+template <int SRC> int pick_base(const frt_ctx *c, int integrator, int flags, bool f64, bool env, Launcher &L);   // piece 0
 // the path kernels of the material sets with every material, one function a part
-template <int SRC> int pick_all(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // piece 1
-template <int SRC> int pick_all_env(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);   // piece 2
-template <int SRC> int pick_nee(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L);       // piece 3
+template <int SRC> int pick_all(const frt_ctx *c, int flags, bool f64, int features, Launcher &L);       // piece 1
+template <int SRC> int pick_all_env(const frt_ctx *c, int flags, bool f64, int features, Launcher &L);   // piece 2
+template <int SRC> int pick_nee(const frt_ctx *c, int flags, bool f64, int features, Launcher &L);       // piece 3
 #define FRT_SPARSE_DECLARE(SRC)                                                                   \
-    template <> int pick_base<SRC>(const frt_ctx *, int, int, bool, bool, SparseLauncher &);      \
-    template <> int pick_all<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);             \
-    template <> int pick_all_env<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);         \
-    template <> int pick_nee<SRC>(const frt_ctx *, int, bool, int, SparseLauncher &);
+    template <> int pick_base<SRC>(const frt_ctx *, int, int, bool, bool, Launcher &);      \
+    template <> int pick_all<SRC>(const frt_ctx *, int, bool, int, Launcher &);             \
+    template <> int pick_all_env<SRC>(const frt_ctx *, int, bool, int, Launcher &);         \
+    template <> int pick_nee<SRC>(const frt_ctx *, int, bool, int, Launcher &);
 FRT_SPARSE_DECLARE(kSrcPixels)
 FRT_SPARSE_DECLARE(kSrcRays)
 #undef FRT_SPARSE_DECLARE
 }  // namespace frt_sparse
 #pragma GCC visibility pop
-using frt_sparse::SparseLauncher;
 using frt_sparse::kSrcPixels;
 using frt_sparse::kSrcRays;
 
@@ -115,6 +107,7 @@ namespace film_reduce {
 // SRC = kSrcRays: the list holds first rays.  A sample starts with ray_begin on its entry's record
 // (read again at every start: 32 bytes that stay in L2, against a path's traversal), the stream
 // id of the record keys its RNG, and the item state keeps no pixel (kIsPix, kIsPx, kIsPy unused).
+// A copy of path_megakernel's loop, not a shared one: a change there goes here too (DESIGN.md "One device loop")
 template <int STACK, int WORLD, int MATS, int KIND, typename R, int SRC = kSrcPixels>
 __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const SparseWork W)
 {
@@ -256,11 +249,11 @@ __global__ __launch_bounds__(kBlock) void sparse_kernel(const DevScene S0, const
 }  // namespace film_reduce
 
 template <int STACK, int WORLD, int MATS, int KIND, typename R, int SRC>
-SparseLauncher make_sparse()
+Launcher make_sparse()
 {
-    SparseLauncher L;
+    Launcher L;   // the scene stays in HBM and there is no register cap: waves 0, lds_scene false, scene_lds 0
     L.fn = reinterpret_cast<const void *>(&film_reduce::sparse_kernel<STACK, WORLD, MATS, KIND, R, SRC>);
-    L.lds = lds_block_bytes(STACK, 0, WORLD != FRT_WORLD_LIST);   // the scene stays in HBM
+    L.lds = lds_block_bytes(STACK, 0, WORLD != FRT_WORLD_LIST);
     L.stack = STACK;
     L.wide = WORLD == kWorldBvh4;
     L.f64 = kIsF64<R>;
@@ -269,7 +262,7 @@ SparseLauncher make_sparse()
 
 // the rung of the context's scene with the scene in HBM
 template <int MATS, int KIND, int SRC>
-int sparse_plan(const frt_ctx *c, int flags, bool f64, SparseLauncher &L)
+int sparse_plan(const frt_ctx *c, int flags, bool f64, Launcher &L)
 {
     if (f64) {   // plan_f64's rungs
         if constexpr (KIND == FRT_INTEGRATOR_PATH) {
@@ -293,7 +286,7 @@ int sparse_plan(const frt_ctx *c, int flags, bool f64, SparseLauncher &L)
     });
 }
 template <int BASE, int SRC>
-int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L)
+int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, Launcher &L)
 {
     switch (features) {
     case 0: return sparse_plan<BASE, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);
@@ -307,7 +300,7 @@ int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, Sp
 
 // the pieces of one source: 0 lambertian and AO, 1 .. 3 the material sets with every material
 #define FRT_SPARSE_PIECE0(SRC)                                                                                                   \
-    template <> int frt_sparse::pick_base<SRC>(const frt_ctx *c, int integrator, int flags, bool f64, bool env, SparseLauncher &L) \
+    template <> int frt_sparse::pick_base<SRC>(const frt_ctx *c, int integrator, int flags, bool f64, bool env, Launcher &L) \
     {                                                                                                                            \
         if (integrator == FRT_INTEGRATOR_AO)                                                                                     \
             return env ? sparse_plan<kMatsAll | kMatsEnv, FRT_INTEGRATOR_AO, SRC>(c, flags, false, L)                            \
@@ -315,7 +308,7 @@ int sparse_plan_features(const frt_ctx *c, int flags, bool f64, int features, Sp
         return sparse_plan<kMatsNone, FRT_INTEGRATOR_PATH, SRC>(c, flags, f64, L);                                               \
     }
 #define FRT_SPARSE_PIECE(NAME, BASE, SRC)                                                                        \
-    template <> int frt_sparse::NAME<SRC>(const frt_ctx *c, int flags, bool f64, int features, SparseLauncher &L) \
+    template <> int frt_sparse::NAME<SRC>(const frt_ctx *c, int flags, bool f64, int features, Launcher &L) \
     {                                                                                                            \
         return sparse_plan_features<BASE, SRC>(c, flags, f64, features, L);                                      \
     }
@@ -402,7 +395,7 @@ int ray_err(frt_ctx *c, int code, const std::string &m)
 }
 
 template <int SRC>
-int pick_sparse(const frt_ctx *c, int integrator, int flags, bool f64, bool env_sampling, SparseLauncher &L)
+int pick_sparse(const frt_ctx *c, int integrator, int flags, bool f64, bool env_sampling, Launcher &L)
 {
     const bool env = c->env_texels != nullptr;
     if (integrator == FRT_INTEGRATOR_AO) return frt_sparse::pick_base<SRC>(c, integrator, flags, false, env, L);
@@ -413,17 +406,14 @@ int pick_sparse(const frt_ctx *c, int integrator, int flags, bool f64, bool env_
     return frt_sparse::pick_base<SRC>(c, integrator, flags, f64, env, L);
 }
 
-template <typename T>
-int grow(frt_ctx *c, T *&buf, size_t &have, size_t bytes)
+// the first entry of a pixel list that lies outside the frame: its refusal's text ("": none does)
+std::string bad_pixel(const std::string &who, const frt_render_params *p, const int32_t *pixels, int64_t npix)
 {
-    bytes = std::max<size_t>(bytes, 16);
-    if (bytes <= have) return FRT_OK;
-    if (buf) HIPCHK(c, hipFree(buf));
-    buf = nullptr;
-    have = 0;
-    HIPCHK(c, hipMalloc((void **)&buf, bytes));
-    have = bytes;
-    return FRT_OK;
+    const int64_t n = (int64_t)p->nx * p->ny;
+    for (int64_t i = 0; i < npix; ++i)
+        if (pixels[i] < 0 || pixels[i] >= n)
+            return who + ": entry " + std::to_string(i) + " is pixel " + std::to_string(pixels[i]) + ", outside [0, nx * ny)";
+    return "";
 }
 
 // what can be refused without a context or a device: the request and the list (host memory)
@@ -450,14 +440,8 @@ int check_request(frt_ctx *c, const frt_render_params *p, const int32_t *pixels_
     if (want_var && *n_chunks < 2)
         return set_err(c, FRT_E_INVALID, who + ": the variance needs at least 2 chunks a pixel; pass samples_per_item "
                                                "< spp (e.g. spp / 2)");
-    if (pixels_host) {
-        const int64_t n = (int64_t)p->nx * p->ny;
-        for (int64_t i = 0; i < npix; ++i)
-            if (pixels_host[i] < 0 || pixels_host[i] >= n)
-                return set_err(c, FRT_E_INVALID, who + ": entry " + std::to_string(i) + " is pixel " +
-                                                     std::to_string(pixels_host[i]) + ", outside [0, nx * ny)");
-    }
-    return FRT_OK;
+    const std::string bad = pixels_host ? bad_pixel(who, p, pixels_host, npix) : "";
+    return bad.empty() ? FRT_OK : set_err(c, FRT_E_INVALID, bad);
 }
 
 // the list, the outputs: device memory; the request is checked
@@ -466,34 +450,20 @@ template <int SRC>
 int sparse_impl(frt_ctx *c, const frt_render_params *p, const void *list, int64_t npix, int spi, int n_chunks,
                 float *out_rgb, float *out_var, hipStream_t st, frt_stats *stats)
 {
-    const auto t_start = std::chrono::steady_clock::now();
-    bool env_sampling = false;
-    if ((p->flags & FRT_FLAG_ENV_SAMPLING) && p->integrator == FRT_INTEGRATOR_PATH && c->env_texels) {
-        if (const int trc = env_tables(c)) return trc;
-        env_sampling = c->env_tab == frt_ctx::kEnvTabBuilt;
-    }
-    if (p->integrator == FRT_INTEGRATOR_AO && c->has_metal)
-        return set_err(c, FRT_E_UNSUPPORTED, "ao integrator: metal has no sampling pdf (constant_pdf::generate)");
-    const bool f64 = use_f64(c, p);
-    if (f64 && !c->has_f64)
-        return set_err(c, FRT_E_INVALID, "fp64 render of a scene uploaded without fp64 records: frt_set_precision(FRT_PRECISION_FP64) "
-                                         "before frt_upload_scene");
-    SparseLauncher L;
+    Persist P;
+    bool env_sampling = false, f64 = false;
+    if (const int rc = render_preamble(c, p, &env_sampling, &f64)) return rc;
+    Launcher L;
     if (pick_sparse<SRC>(c, p->integrator, p->flags, f64, env_sampling, L) != FRT_OK || !L.fn)
         return set_err(c, FRT_E_UNSUPPORTED, "BVH deeper than 63 levels");
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, L.fn, kBlock, L.lds) != hipSuccess || bpc <= 0) bpc = 1;
     const uint64_t npad = ((uint64_t)npix + 63) & ~63ull;
     const uint64_t n_items = npad * (uint64_t)n_chunks;
-    const int grid = (int)std::min<uint64_t>((uint64_t)c->n_cu * bpc, (n_items + kBlock - 1) / kBlock);
-    const size_t n_waves = (size_t)grid * kBlock / 64;
-    const uint32_t grab = kQueueGrab;
-    // the 32-bit queue head runs past n_items by at most one grab per wave (render_impl's check)
-    if (n_items + (uint64_t)n_waves * (grab + 64) >= 0xffffffffULL)
-        return set_err(c, FRT_E_UNSUPPORTED, std::string(SRC == kSrcRays ? "radiance_rays" : "render_pixels") +
-                                                 ": list too long for one call: split it");
-    if (const int rc = grow(c, c->sp_partial, c->sp_partial_bytes, (size_t)n_items * 3 * sizeof(float))) return rc;
-    if (const int rc = grow(c, c->sp_wave_rays, c->sp_wave_rays_bytes, n_waves * 4 * sizeof(unsigned long long))) return rc;
+    if (const int rc = persist_plan(c, L.fn, L.lds, (int64_t)((n_items + kBlock - 1) / kBlock), &c->sp_wave_rays, P)) return rc;
+    // the queue head runs past n_items by at most one grab per wave
+    if (const int rc = queue_headroom(c, P, n_items, kQueueGrab + 64, std::string(SRC == kSrcRays ? "radiance_rays" : "render_pixels") +
+                                                                    ": list too long for one call: split it"))
+        return rc;
+    if (const int rc = c->sp_partial.reserve(c, (size_t)n_items * 3 * sizeof(float))) return rc;
     SparseWork W{};
     W.nx = p->nx; W.ny = p->ny; W.spp = p->spp; W.max_depth = p->max_depth; W.seed = p->seed;
     W.s_off = (uint32_t)p->sample_offset;
@@ -506,90 +476,24 @@ int sparse_impl(frt_ctx *c, const frt_render_params *p, const void *list, int64_
     W.partial = c->sp_partial;
     W.counter = c->counter + kSparseCounterWord;   // a queue word of its own
     W.wave_rays = c->sp_wave_rays;
-    W.grab = grab;
-    HIPCHK(c, hipMemsetAsync(W.counter, 0, sizeof(unsigned), st));
-    HIPCHK(c, hipEventRecord(c->ev0, st));
+    W.grab = kQueueGrab;
     DevScene Sarg = c->S;
     void *args[] = {&Sarg, &W};
-    const hipError_t le = hipLaunchKernel(L.fn, dim3(grid), dim3(kBlock), args, L.lds, st);
-    if (le != hipSuccess) return set_err(c, FRT_E_HIP, std::string("sparse_kernel launch: ") + hipGetErrorString(le));
-    hipLaunchKernelGGL(film_reduce::sparse_reduce, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, c->sp_partial, out_rgb, out_var,
-                       W.npix, W.npad, n_chunks, p->spp, spi, SRC == kSrcRays ? 1 : 0);
+    if (const int rc = persist_launch(c, P, "sparse_kernel", L.fn, L.lds, args, W.counter, sizeof(unsigned), st)) return rc;
+    hipLaunchKernelGGL(film_reduce::sparse_reduce, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, c->sp_partial.get(), out_rgb,
+                       out_var, W.npix, W.npad, n_chunks, p->spp, spi, SRC == kSrcRays ? 1 : 0);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    std::vector<unsigned long long> wr(n_waves * 4);
-    HIPCHK(c, hipMemcpyAsync(wr.data(), c->sp_wave_rays, wr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HIPCHK(c, hipEventRecord(c->ev1, st));   // kernel_ms: the render with its reduction
+    if (const int rc = persist_finish(c, P, c->sp_wave_rays, st, stats)) return rc;
     if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        for (size_t w = 0; w < n_waves; ++w) {
-            stats->camera_rays += wr[4 * w]; stats->extension_rays += wr[4 * w + 1];
-            stats->shadow_rays += wr[4 * w + 2]; stats->samples += wr[4 * w + 3];
-        }
         stats->pixels = (uint64_t)npix;
         stats->work_items = (uint64_t)npix * n_chunks;
-        stats->stack_entries = (uint32_t)L.stack;
-        stats->bvh_depth = (uint32_t)(L.wide ? c->depth4 : c->stack_needed);
-        stats->scene_bytes = c->scene_lds_bytes;
-        stats->kernel_ms = ms;
-        stats->fp64 = L.f64 ? 1u : 0u;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
+    fill_plan_stats(stats, c, L);
     return FRT_OK;
 }
 
-}  // namespace
-
-extern "C" int frtx_render_pixels_device(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix,
-                                         float *out_rgb, float *out_var, void *hip_stream, frt_stats *st)
-{
-    int spi = 0, n_chunks = 0;
-    if (const int rc = check_request(c, p, nullptr, npix, &spi, &n_chunks, out_var != nullptr)) return rc;
-    if (!c) return FRT_E_INVALID;
-    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
-    if (st) memset(st, 0, sizeof(*st));
-    if (npix == 0) return FRT_OK;
-    if (!pixels || !out_rgb) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // the list is read back and checked before any kernel runs
-    std::vector<int32_t> host((size_t)npix);
-    HIPCHK(c, hipMemcpyAsync(host.data(), pixels, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    if (const int rc = check_request(c, p, host.data(), npix, &spi, &n_chunks, out_var != nullptr)) return rc;
-    return sparse_impl<kSrcPixels>(c, p, pixels, npix, spi, n_chunks, out_rgb, out_var, stream, st);
-}
-
-extern "C" int frtx_render_pixels(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, float *out_rgb,
-                                  float *out_var, frt_stats *st)
-{
-    int spi = 0, n_chunks = 0;
-    if (npix > 0 && !pixels) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
-    if (const int rc = check_request(c, p, pixels, npix, &spi, &n_chunks, out_var != nullptr)) return rc;
-    if (!c) return FRT_E_INVALID;
-    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
-    if (st) memset(st, 0, sizeof(*st));
-    if (npix == 0) return FRT_OK;
-    if (!out_rgb) return set_err(c, FRT_E_INVALID, "render_pixels: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n3 = (size_t)npix * 3;
-    if (const int rc = grow(c, c->sp_pixels, c->sp_pixels_bytes, (size_t)npix * sizeof(int32_t))) return rc;
-    if (const int rc = grow(c, c->sp_out, c->sp_out_bytes, 2 * n3 * sizeof(float))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->sp_pixels, pixels, (size_t)npix * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    const int rc = sparse_impl<kSrcPixels>(c, p, c->sp_pixels, npix, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
-                               c->stream, st);
-    if (rc != FRT_OK) return rc;
-    HIPCHK(c, hipMemcpy(out_rgb, c->sp_out, n3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_var) HIPCHK(c, hipMemcpy(out_var, c->sp_out + n3, n3 * sizeof(float), hipMemcpyDeviceToHost));
-    return FRT_OK;
-}
-
-// ---- a list of first rays (frt.h frtx_radiance_rays) ----
-namespace {
-
-// the request and, when it is in host memory, the list
+// frtx_radiance_rays: the request and, when it is in host memory, the list
 int check_rays(frt_ctx *c, const frt_render_params *p, const float *rays_host, int64_t n, int *spi, int *n_chunks, bool want_var)
 {
     if (!p || n < 0) return ray_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
@@ -603,50 +507,88 @@ int check_rays(frt_ctx *c, const frt_render_params *p, const float *rays_host, i
     return FRT_OK;
 }
 
-}  // namespace
+// What differs between the two kinds of list: the name in the texts, a record (kPer values of T),
+// the check of the request (with the list where it is in host memory) and the context's device
+// copy of a host call's list.  A refusal of the ray calls made without a context keeps its text
+// for frt_last_error(NULL).
+struct PixelList {
+    using T = int32_t;
+    static constexpr int kSrc = kSrcPixels, kPer = 1;
+    static constexpr const char *kWho = "render_pixels";
+    static int check(frt_ctx *c, const frt_render_params *p, const T *host, int64_t n, int *spi, int *n_chunks, bool want_var)
+    {
+        return check_request(c, p, host, n, spi, n_chunks, want_var);
+    }
+    static DevBuf<T> &dev(frt_ctx *c) { return c->sp_pixels; }
+    static int err(frt_ctx *c, int code, const std::string &m) { return set_err(c, code, m); }
+};
+struct RayList {
+    using T = float;
+    static constexpr int kSrc = kSrcRays, kPer = 8;
+    static constexpr const char *kWho = "radiance_rays";
+    static constexpr auto check = check_rays;
+    static DevBuf<T> &dev(frt_ctx *c) { return c->sp_rays; }
+    static constexpr auto err = ray_err;
+};
 
-extern "C" int frtx_radiance_rays_device(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
-                                         float *out_var, void *hip_stream, frt_stats *st)
+// The four list entry points.  device: the list and the outputs are device memory and the call
+// runs on the caller's stream; else they are host memory, copied through the context's buffers.
+template <typename L>
+int list_call(frt_ctx *c, const frt_render_params *p, const typename L::T *list, int64_t n, float *out_rgb, float *out_var,
+              bool device, void *hip_stream, frt_stats *st)
 {
+    const std::string who = L::kWho;
     int spi = 0, n_chunks = 0;
-    if (const int rc = check_rays(c, p, nullptr, n, &spi, &n_chunks, out_var != nullptr)) return rc;
-    if (!c) return ray_err(c, FRT_E_INVALID, "radiance_rays: null context");
+    if (!device && n > 0 && !list) return L::err(c, FRT_E_INVALID, who + ": bad arguments");
+    if (const int rc = L::check(c, p, device ? nullptr : list, n, &spi, &n_chunks, out_var != nullptr)) return rc;
+    if (!c) return L::kSrc == kSrcRays ? L::err(c, FRT_E_INVALID, who + ": null context") : FRT_E_INVALID;
     if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
     if (st) memset(st, 0, sizeof(*st));
     if (n == 0) return FRT_OK;
-    if (!rays || !out_rgb) return set_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
+    if (!list || !out_rgb) return set_err(c, FRT_E_INVALID, who + ": bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // the list is read back and checked before any kernel runs
-    std::vector<float> host((size_t)n * 8);
-    HIPCHK(c, hipMemcpyAsync(host.data(), rays, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    if (const int rc = check_rays(c, p, host.data(), n, &spi, &n_chunks, out_var != nullptr)) return rc;
-    return sparse_impl<kSrcRays>(c, p, rays, n, spi, n_chunks, out_rgb, out_var, stream, st);
-}
-
-extern "C" int frtx_radiance_rays(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
-                                  float *out_var, frt_stats *st)
-{
-    int spi = 0, n_chunks = 0;
-    if (n > 0 && !rays) return ray_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
-    if (const int rc = check_rays(c, p, rays, n, &spi, &n_chunks, out_var != nullptr)) return rc;
-    if (!c) return ray_err(c, FRT_E_INVALID, "radiance_rays: null context");
-    if (!c->have_scene) return set_err(c, FRT_E_NO_SCENE, "no scene uploaded");
-    if (st) memset(st, 0, sizeof(*st));
-    if (n == 0) return FRT_OK;
-    if (!out_rgb) return set_err(c, FRT_E_INVALID, "radiance_rays: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n3 = (size_t)n * 3, ray_bytes = (size_t)n * 8 * sizeof(float);
-    if (const int rc = grow(c, c->sp_rays, c->sp_rays_bytes, ray_bytes)) return rc;
-    if (const int rc = grow(c, c->sp_out, c->sp_out_bytes, 2 * n3 * sizeof(float))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->sp_rays, rays, ray_bytes, hipMemcpyHostToDevice, c->stream));
-    const int rc = sparse_impl<kSrcRays>(c, p, c->sp_rays, n, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr,
-                                         c->stream, st);
+    const size_t n3 = (size_t)n * 3, list_bytes = (size_t)n * L::kPer * sizeof(typename L::T);
+    if (device) {
+        hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        // the list is read back and checked before any kernel runs
+        std::vector<typename L::T> host((size_t)n * L::kPer);
+        HIPCHK(c, hipMemcpyAsync(host.data(), list, list_bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(c, hipStreamSynchronize(stream));
+        if (const int rc = L::check(c, p, host.data(), n, &spi, &n_chunks, out_var != nullptr)) return rc;
+        return sparse_impl<L::kSrc>(c, p, list, n, spi, n_chunks, out_rgb, out_var, stream, st);
+    }
+    DevBuf<typename L::T> &dev = L::dev(c);
+    if (const int rc = dev.reserve(c, list_bytes)) return rc;
+    if (const int rc = c->sp_out.reserve(c, 2 * n3 * sizeof(float))) return rc;
+    HIPCHK(c, hipMemcpyAsync(dev, list, list_bytes, hipMemcpyHostToDevice, c->stream));
+    const int rc = sparse_impl<L::kSrc>(c, p, dev.get(), n, spi, n_chunks, c->sp_out, out_var ? c->sp_out + n3 : nullptr, c->stream, st);
     if (rc != FRT_OK) return rc;
     HIPCHK(c, hipMemcpy(out_rgb, c->sp_out, n3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_var) HIPCHK(c, hipMemcpy(out_var, c->sp_out + n3, n3 * sizeof(float), hipMemcpyDeviceToHost));
     return FRT_OK;
+}
+
+}  // namespace
+
+extern "C" int frtx_render_pixels_device(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix,
+                                         float *out_rgb, float *out_var, void *hip_stream, frt_stats *st)
+{
+    return list_call<PixelList>(c, p, pixels, npix, out_rgb, out_var, true, hip_stream, st);
+}
+extern "C" int frtx_render_pixels(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix, float *out_rgb,
+                                  float *out_var, frt_stats *st)
+{
+    return list_call<PixelList>(c, p, pixels, npix, out_rgb, out_var, false, nullptr, st);
+}
+extern "C" int frtx_radiance_rays_device(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
+                                         float *out_var, void *hip_stream, frt_stats *st)
+{
+    return list_call<RayList>(c, p, rays, n, out_rgb, out_var, true, hip_stream, st);
+}
+extern "C" int frtx_radiance_rays(frt_ctx *c, const frt_render_params *p, const float *rays, int64_t n, float *out_rgb,
+                                  float *out_var, frt_stats *st)
+{
+    return list_call<RayList>(c, p, rays, n, out_rgb, out_var, false, nullptr, st);
 }
 
 extern "C" int frtx_camera_rays_device(frt_ctx *c, const frt_render_params *p, const int32_t *pixels, int64_t npix,
@@ -664,11 +606,8 @@ extern "C" int frtx_camera_rays_device(frt_ctx *c, const frt_render_params *p, c
     std::vector<int32_t> host((size_t)npix);
     HIPCHK(c, hipMemcpyAsync(host.data(), pixels, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
-    const int64_t n = (int64_t)p->nx * p->ny;
-    for (int64_t i = 0; i < npix; ++i)
-        if (host[i] < 0 || host[i] >= n)
-            return set_err(c, FRT_E_INVALID, "camera_rays: entry " + std::to_string(i) + " is pixel " + std::to_string(host[i]) +
-                                                 ", outside [0, nx * ny)");
+    const std::string bad = bad_pixel("camera_rays", p, host.data(), npix);
+    if (!bad.empty()) return set_err(c, FRT_E_INVALID, bad);
     const dim3 grid((unsigned)((npix + 255) / 256)), block(256);
     float4 *out = reinterpret_cast<float4 *>(rays_out);
     if (p->flags & FRT_FLAG_SOBOL)
