@@ -1,6 +1,6 @@
 // frt_lbvh.hip -- GPU BVH builders over the world
 // primitives' boxes, on the device, as fast alternatives to the host SAH builds
-// (parallel_bvh_node::create_bvh, parallel_bvh.h:67-175; host: csrc/host/scene.cpp):
+// (parallel_bvh_node::create_bvh, parallel_bvh.h:67-175; host: csrc/host/bvh_build.cpp):
 // a linear BVH (steps 1-5 below) and PLOC clustering on the same Morton order
 // (steps 1-3, then k_ploc_*; SAH-like quality, the default).
 //
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void k_ploc_merge(const float4 *__restrict_
 // A task is a node over idx[b, e) (sizes >= 2).  One block per task: box and
 // centroid bounds, 32 centroid bins per axis in LDS (ordered-uint min / max
 // atomics), the cheapest split N_L A_L + N_R A_R (the host builder's rule,
-// csrc/host/scene.cpp SahBuilder), then a stable block-wide partition of the
+// csrc/host/bvh_build.cpp Binned), then a stable block-wide partition of the
 // range into idx_out.  Children of two or more prims become next-level tasks;
 // single prims become leaves (~prim).  Node ids are handed out by an atomic
 // counter (their numbering varies, the tree does not).

@@ -1,7 +1,8 @@
 // film.cpp -- the output side of the renderer (what viewer::add_sample,
 // viewer::save_and_destroy and image::save_image do in the reference,
 // viewer.cpp:109-132, image.cpp:24-58): progressive accumulation of passes,
-// the display tonemap and the PNG / BMP writers (zlib deflate for PNG).
+// the display tonemap, the PNG / BMP writers (zlib deflate for PNG) and the
+// PFM writer (image.h:89-118).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -141,4 +142,16 @@ extern "C" int frt_write_image(const char *path, int nx, int ny, const uint8_t *
     if (!f) return FRT_E_IO;
     const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
     return (fclose(f) == 0 && ok) ? FRT_OK : FRT_E_IO;
+}
+
+extern "C" int frt_write_pfm(const char *path, int nx, int ny, const float *rgb)
+{
+    if (!path || !rgb || nx <= 0 || ny <= 0) return FRT_E_INVALID;
+    FILE *f = fopen(path, "wb");
+    if (!f) return FRT_E_IO;
+    fprintf(f, "PF\n%d %d\n-1\n", nx, ny);
+    const size_t n = (size_t)nx * ny * 3;
+    const bool ok = fwrite(rgb, sizeof(float), n, f) == n;
+    fclose(f);
+    return ok ? FRT_OK : FRT_E_IO;
 }

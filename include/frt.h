@@ -475,7 +475,12 @@ typedef struct frt_host_scene_info {
     double load_ms, build_ms;
 } frt_host_scene_info;
 /* kind: "cornell_box_obj" (main.cpp:222-252), "veach_mis" (main.cpp:281-314),
- *       "obj_geo" / "obj_smooth" (any OBJ, cornell camera, geometric / vertex normals) */
+ *       "obj_geo" / "obj_smooth" (any OBJ, cornell camera, geometric / vertex normals)
+ * FRT_E_IO: unreadable file.  FRT_E_INVALID, and no scene: unknown kind, or a face of
+ * the file with a vertex or normal index that is no number, 0, outside [1, count]
+ * (negative: below -count) or not representable -- the reference's importer fails on
+ * such a file.  A texture index that is missing or out of range only means no uv for
+ * its mesh. */
 int frt_scene_create(const char *kind, const char *obj_path, double aspect, frt_host_scene **out);
 int frt_scene_view_get(const frt_host_scene *s, frt_scene_view *view);
 
@@ -490,7 +495,8 @@ int frt_scene_view_get(const frt_host_scene *s, frt_scene_view *view);
  * material every mesh of the file takes, or NULL for the file's MTL materials
  * (mesh_loader.cpp:59-112); meshes whose material is a diffuse_light join
  * Scene::lights.  Returns FRT_E_IO (unreadable file) or FRT_E_INVALID (singular
- * matrix, bad material). */
+ * matrix, bad material, a face index the file does not have: frt_scene_create's
+ * rule); a refused file adds nothing, the scene is what it was before the call. */
 enum { FRT_SPHERE_WORLD = 1, FRT_SPHERE_LIGHTS = 2, FRT_SPHERE_BOTH = 3 };
 int frt_scene_new(frt_host_scene **out);
 int frt_scene_add_obj(frt_host_scene *s, const char *obj_path, const double *to_world16, const frt_material *bsdf,
@@ -539,7 +545,11 @@ int frt_scene_info(const frt_host_scene *s, frt_host_scene_info *info);
 void frt_scene_destroy(frt_host_scene *s);
 
 /* cornell_1m generator: every non-emissive quad of `src_obj` bilinearly
- * tessellated into k x k cells, written as OBJ + MTL. */
+ * tessellated into k x k cells, written as OBJ + MTL.
+ * FRT_E_IO: a file cannot be read or written.  FRT_E_INVALID: k < 1, or a face
+ * with a vertex index that frt_scene_create refuses (a token that is no number
+ * included); what dst_obj then holds is unspecified.  A face keeps its first 64
+ * corners, as in the importer. */
 int frt_write_tessellated_obj(const char *src_obj, int k, const char *dst_obj);
 
 /* Radiance RGBE (.hdr) reader: what stbi_loadf gives the reference's

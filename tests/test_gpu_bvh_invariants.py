@@ -4,14 +4,14 @@ The GPU builders' node boxes (k_refit's acquire / release handshake between sibl
 k_ploc_merge, k_sah_level: csrc/frt_lbvh.hip) go into the scene unchanged, and films judge
 them only at RMSE 1e-4 to 1e-3: a box a few ulps short loses a handful of rays and passes.
 Here every node's box must EQUAL the union of the outward-rounded fp32 boxes of the primitives
-beneath it (f_down / f_up of csrc/host/scene.cpp; min and max are exact, so equality is the
-test), a second build must give the same tree, and the tree must answer rays as the list of
+beneath it (f_down / f_up of frt_scene_build_bvh_gpu_algo, csrc/host/scene.cpp, over the fp64 boxes
+of csrc/host/bvh_build.cpp prim_boxes; min and max are exact, so equality is the test), a second build must give the same tree, and the tree must answer rays as the list of
 its primitives does (trace_rays.gate_exact).  Inputs: Cornell, its tessellations, veach_mis
 (spheres) and the degenerate sets a builder meets first -- 2 and 3 primitives, 64 copies of
 one triangle (every Morton code equal, every SAH bin but one empty), 300 triangles in one
 plane (no extent on an axis), 257 triangles (one over a block).
 
-CPU: the host builders' trees (build_bvh_sah, the reference topology) keep fp64 boxes, which
+CPU: the host builders' trees (csrc/host/bvh_build.cpp: build_bvh_sah, the reference topology) keep fp64 boxes, which
 must contain those unions' fp64 sources."""
 import numpy as np
 import pytest
