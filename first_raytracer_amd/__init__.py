@@ -35,6 +35,8 @@ FRT_FLAG_FP32 = 1024
 FRT_FLAG_ENV_SAMPLING = 2048   # path: next-event estimation toward the environment image (frt.h)
 FRT_FLAG_ROULETTE = 4096       # path: Russian roulette from the fourth vertex on (frt.h)
 FRT_FLAG_SOBOL = 8192          # path: Owen-scrambled Sobol' sample points (frt.h)
+FRTX_PRT_UNSHADOWED = 1 << 16  # prt_transfer: bounce 0 without visibility rays (frt.h)
+PRT_COEFFS = 25                # 5 SH bands, index l (l + 1) + m
 FRT_PRECISION_AUTO, FRT_PRECISION_FP32, FRT_PRECISION_FP64 = 0, 1, 2
 FRT_GPU_BVH_PLOC = 0
 FRT_GPU_BVH_LBVH = 1
@@ -245,7 +247,10 @@ EXPORTS = ("frt_get_abi_version", "frt_create", "frt_destroy", "frt_last_error",
 EXPORTS_X = ("frtx_selftest_tree_refine", "frtx_selftest_trace_host", "frtx_selftest_chunk_variance",
              "frtx_selftest_plan", "frtx_selftest_shadow_tree", "frtx_render_pixels", "frtx_render_pixels_device",
              "frtx_selftest_exit_tree", "frtx_radiance_rays", "frtx_radiance_rays_device", "frtx_camera_rays_device",
-             "frtx_selftest_radiance_host", "frtx_selftest_camera_rays_host")
+             "frtx_selftest_radiance_host", "frtx_selftest_camera_rays_host",
+             "frtx_prt_basis", "frtx_sh_project_image", "frtx_prt_sample_dirs", "frtx_prt_corners", "frtx_prt_transfer",
+             "frtx_prt_transfer_device", "frtx_prt_rays", "frtx_prt_rays_device", "frtx_selftest_prt_transfer_host",
+             "frtx_selftest_prt_rays_host", "frtx_prt_render", "frtx_selftest_prt_budget")
 
 
 def lib():
@@ -334,6 +339,21 @@ def lib():
                                                   ctypes.POINTER(Image), vp, ctypes.POINTER(Stats)]
         L.frtx_selftest_camera_rays_host.argtypes = [ctypes.POINTER(SceneView), ctypes.POINTER(RenderParams), vp,
                                                      ctypes.c_int64, vp]
+    if hasattr(L, "frtx_prt_transfer"):   # (FRT_LIB_PATH may name an earlier revision's build for a timing A/B)
+        sv = ctypes.POINTER(SceneView)
+        L.frtx_prt_basis.argtypes = [vp, ctypes.c_int64, vp]
+        L.frtx_sh_project_image.argtypes = [ctypes.POINTER(Image), vp, vp]
+        L.frtx_prt_sample_dirs.argtypes = [ctypes.c_int, ctypes.c_uint32, vp]
+        L.frtx_prt_corners.argtypes = [sv, vp, vp]
+        L.frtx_prt_transfer.argtypes = [vp, sv, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(Stats)]
+        L.frtx_prt_transfer_device.argtypes = [vp, sv, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp,
+                                               ctypes.POINTER(Stats)]
+        L.frtx_prt_rays.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(Stats)]
+        L.frtx_prt_rays_device.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.POINTER(Stats)]
+        L.frtx_selftest_prt_transfer_host.argtypes = [sv, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp]
+        L.frtx_selftest_prt_rays_host.argtypes = [sv, ctypes.POINTER(Image), vp, vp, vp, ctypes.c_int64, vp]
+        L.frtx_prt_render.argtypes = [vp, ctypes.POINTER(RenderParams), vp, vp, vp, ctypes.POINTER(Stats)]
+        L.frtx_selftest_prt_budget.argtypes = [ctypes.c_int64]
     _lib = L
     return L
 
@@ -343,7 +363,7 @@ def _check(rc, what, ctx=None):
         msg = ""
         if ctx is not None:
             msg = lib().frt_last_error(ctx).decode(errors="replace")
-        elif "_rays" in what or "radiance" in what:   # hooks without a context: frt_last_error(NULL) has their text
+        elif "_rays" in what or "radiance" in what or "prt" in what or "sh_project" in what:   # hooks without a context: frt_last_error(NULL) has their text
             msg = lib().frt_last_error(None).decode(errors="replace")
         raise FrtError(f"{what} failed: {ERRORS.get(rc, rc)} {msg}")
 
@@ -514,6 +534,7 @@ class Context:
         with Context.set_env_image stays until that call changes it."""
         view = scene.view() if isinstance(scene, HostScene) else scene
         _check(lib().frt_upload_scene(self.ptr, ctypes.byref(view)), "frt_upload_scene", self.ptr)
+        self._n_tris = int(view.n_tris)   # prt_rays checks the size of its T against it
         img = scene.env_image() if isinstance(scene, HostScene) else None
         if img is not None:
             _check(lib().frt_set_env_image(self.ptr, ctypes.byref(img)), "frt_set_env_image", self.ptr)
@@ -624,6 +645,77 @@ class Context:
             jitter = None if passes == 1 else np.random.default_rng([int(params.seed), k]).random(2)
             rgb, _, st = self.radiance_rays(p, make_rays(jitter), variance=False)
             acc = rgb if acc is None else film_accumulate(acc, k * params.spp, rgb, params.spp)
+        return acc, st
+
+    def prt_transfer(self, scene, dirs, bounces=0, flags=0, budget=None):
+        """frtx_prt_transfer: the diffuse transfer vectors of the uploaded scene, T (n_tris, 3, 25, 3)
+        float32 -- per triangle corner, SH coefficient and channel --, summed over `bounces`
+        interreflections.  scene: the HostScene (or SceneView) that was uploaded; dirs: (n, 3) float32
+        unit directions (prt_sample_dirs); flags: FRTX_PRT_UNSHADOWED, FRT_FLAG_BVH2.  budget: bytes
+        of chunk sums one batch of corners may take (a test knob; the result does not depend on it).
+        Returns (T, stats)."""
+        view = _view(scene)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        T = np.zeros((int(view.n_tris), 3, PRT_COEFFS, 3), np.float32)
+        st = Stats()
+        with _prt_budget(budget):
+            _check(lib().frtx_prt_transfer(self.ptr, ctypes.byref(view), dirs.ctypes.data, len(dirs), int(bounces), int(flags),
+                                           T.ctypes.data, ctypes.byref(st)), "frtx_prt_transfer", self.ptr)
+        return T, st
+
+    def prt_transfer_device(self, scene, dirs, bounces=0, flags=0):
+        """frtx_prt_transfer_device: prt_transfer into device memory; returns (T as a torch tensor
+        on this context's device, stats)."""
+        import torch
+        view = _view(scene)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        T = torch.zeros((int(view.n_tris), 3, PRT_COEFFS, 3), dtype=torch.float32, device=torch.device("cuda", self.device))
+        st = Stats()
+        _check(lib().frtx_prt_transfer_device(self.ptr, ctypes.byref(view), dirs.ctypes.data, len(dirs), int(bounces),
+                                              int(flags), T.data_ptr(), None, ctypes.byref(st)),
+               "frtx_prt_transfer_device", self.ptr)
+        return T, st
+
+    def prt_rays(self, T, li, rays):
+        """frtx_prt_rays: PRT shading along rays -- the closest hit of each ((n, 8) float32 records,
+        ray_records() / camera_rays() / first_raytracer_amd.cameras), then on a lambertian triangle the
+        dot product of li (sh_project_image, (25, 3)) with the transfer T interpolated at the hit, on
+        an emitter its emission, on a miss the context's environment.  Returns (rgb (n, 3), stats)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        li = np.ascontiguousarray(li, dtype=np.float32).reshape(-1)
+        if li.size != 3 * PRT_COEFFS:
+            raise ValueError("li: (25, 3) coefficients")
+        if hasattr(self, "_n_tris") and T.size != self._n_tris * 9 * PRT_COEFFS:
+            raise ValueError("T: (n_tris, 3, 25, 3) of the uploaded scene")
+        rgb = np.zeros((len(rays), 3), np.float32)
+        st = Stats()
+        _check(lib().frtx_prt_rays(self.ptr, T.ctypes.data, li.ctypes.data, rays.ctypes.data, len(rays), rgb.ctypes.data,
+                                   ctypes.byref(st)), "frtx_prt_rays", self.ptr)
+        return rgb, st
+
+    def render_prt(self, params, T, li, make_rays=None):
+        """A PRT image: per sample s of params.spp the camera's first rays (camera_rays at sample
+        sample_offset + s: the film and lens points a path render takes) shaded by prt_rays, the
+        samples averaged by film_accumulate's rule.  make_rays(jitter) -> (n, 8) records, a camera of
+        first_raytracer_amd.cameras, replaces the scene's camera (jitter hashed from (seed, s), the
+        texel centres for a single sample).  Returns (film (ny, nx, 3) float32, y = 0 the bottom row
+        -- with make_rays (n, 3) in the camera's order --, stats of the last sample)."""
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        li = np.ascontiguousarray(li, dtype=np.float32).reshape(-1)
+        if li.size != 3 * PRT_COEFFS or (hasattr(self, "_n_tris") and T.size != self._n_tris * 9 * PRT_COEFFS):
+            raise ValueError("T: (n_tris, 3, 25, 3) of the uploaded scene, li: (25, 3)")
+        st = Stats()
+        if make_rays is None:   # frtx_prt_render: the same composition inside the library
+            film = np.zeros((params.ny, params.nx, 3), np.float32)
+            _check(lib().frtx_prt_render(self.ptr, ctypes.byref(params), T.ctypes.data, li.ctypes.data, film.ctypes.data,
+                                         ctypes.byref(st)), "frtx_prt_render", self.ptr)
+            return film, st
+        acc = None
+        for s in range(int(params.spp)):
+            rays = make_rays(None if params.spp == 1 else np.random.default_rng([int(params.seed), s]).random(2))
+            rgb, st = self.prt_rays(T, li, rays)
+            acc = rgb if acc is None else film_accumulate(acc, s, rgb, 1)
         return acc, st
 
     def render_until(self, params, target, max_spp, first_spp=None, adaptive=False, switch=None):
@@ -972,6 +1064,97 @@ def selftest_radiance_host(scene, params, rays, env_image=None):
     _check(lib().frtx_selftest_radiance_host(ctypes.byref(view), ctypes.byref(params), rays.ctypes.data, len(rays), desc,
                                              out.ctypes.data, ctypes.byref(st)), "frtx_selftest_radiance_host")
     return out, st
+
+
+def _view(scene):
+    """The SceneView of a HostScene, or the view itself."""
+    return scene.view() if hasattr(scene, "view") else scene
+
+
+class _prt_budget:
+    """The batch budget of prt_transfer and its replay in bytes (frtx_selftest_prt_budget) for the calls inside."""
+
+    def __init__(self, budget):
+        self.budget = budget
+
+    def __enter__(self):
+        if self.budget is not None:
+            _check(lib().frtx_selftest_prt_budget(int(self.budget)), "frtx_selftest_prt_budget")
+
+    def __exit__(self, *exc):
+        if self.budget is not None:
+            lib().frtx_selftest_prt_budget(0)
+
+
+def prt_basis(dirs):
+    """frtx_prt_basis: Y (n, 25) float32 of unit directions (n, 3) -- the real SH basis in the
+    environment image's convention, fp64 rounded once: the table prt_transfer reads."""
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    Y = np.zeros((len(dirs), PRT_COEFFS), np.float32)
+    _check(lib().frtx_prt_basis(dirs.ctypes.data, len(dirs), Y.ctypes.data), "frtx_prt_basis")
+    return Y
+
+
+def sh_project_image(image=None, env_color=None):
+    """frtx_sh_project_image: li (25, 3) float64 of an environment image ((ny, nx, 3) uint8 sRGB or
+    float32) or, without one, of the constant colour."""
+    li = np.zeros((PRT_COEFFS, 3), np.float64)
+    if image is None:
+        e = np.ascontiguousarray(env_color, dtype=np.float64).reshape(3)
+        _check(lib().frtx_sh_project_image(None, e.ctypes.data, li.ctypes.data), "frtx_sh_project_image")
+        return li
+    a, fmt = image_array({"data": image})
+    desc = Image(a.shape[1], a.shape[0], fmt, 0, a.ctypes.data)
+    _check(lib().frtx_sh_project_image(ctypes.byref(desc), None, li.ctypes.data), "frtx_sh_project_image")
+    return li
+
+
+def prt_sample_dirs(sqrt_n, seed=0):
+    """frtx_prt_sample_dirs: (sqrt_n^2, 3) float32 unit directions, one per jittered stratum,
+    uniform on the sphere."""
+    dirs = np.zeros((int(sqrt_n) ** 2 if sqrt_n >= 1 else 1, 3), np.float32)
+    _check(lib().frtx_prt_sample_dirs(int(sqrt_n), int(seed), dirs.ctypes.data), "frtx_prt_sample_dirs")
+    return dirs
+
+
+def prt_corners(scene):
+    """frtx_prt_corners: (origin (n_tris, 3, 3), normal (n_tris, 3, 3), albedo (n_tris, 3, 3)) float32,
+    the corner records prt_transfer traces from."""
+    view = _view(scene)
+    on = np.zeros((int(view.n_tris), 3, 8), np.float32)
+    rho = np.zeros((int(view.n_tris), 3, 3), np.float32)
+    _check(lib().frtx_prt_corners(ctypes.byref(view), on.ctypes.data, rho.ctypes.data), "frtx_prt_corners")
+    return on[..., 0:3].copy(), on[..., 4:7].copy(), rho
+
+
+def selftest_prt_transfer_host(scene, dirs, bounces=0, flags=0, budget=None):
+    """Context.prt_transfer through the same code on the host (frtx_selftest_prt_transfer_host):
+    T (n_tris, 3, 25, 3) float32.  T is created filled with NaN: a refused call writes nothing."""
+    view = _view(scene)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    T = np.full((int(view.n_tris), 3, PRT_COEFFS, 3), np.nan, np.float32)
+    with _prt_budget(budget):
+        _check(lib().frtx_selftest_prt_transfer_host(ctypes.byref(view), dirs.ctypes.data, len(dirs), int(bounces), int(flags),
+                                                     T.ctypes.data), "frtx_selftest_prt_transfer_host")
+    return T
+
+
+def selftest_prt_rays_host(scene, T, li, rays, env_image=None):
+    """Context.prt_rays through the same code on the host (frtx_selftest_prt_rays_host): rgb (n, 3)."""
+    view = _view(scene)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    T = np.ascontiguousarray(T, dtype=np.float32)
+    li = np.ascontiguousarray(li, dtype=np.float32).reshape(-1)
+    if li.size != 3 * PRT_COEFFS or T.size != int(view.n_tris) * 9 * PRT_COEFFS:
+        raise ValueError("T: (n_tris, 3, 25, 3) of the scene, li: (25, 3)")
+    rgb = np.zeros((len(rays), 3), np.float32)
+    desc = None
+    if env_image is not None:
+        a, fmt = image_array({"data": env_image})
+        desc = ctypes.byref(Image(a.shape[1], a.shape[0], fmt, 0, a.ctypes.data))
+    _check(lib().frtx_selftest_prt_rays_host(ctypes.byref(view), desc, T.ctypes.data, li.ctypes.data, rays.ctypes.data,
+                                             len(rays), rgb.ctypes.data), "frtx_selftest_prt_rays_host")
+    return rgb
 
 
 def selftest_camera_rays_host(scene, params, pixels):

@@ -77,6 +77,15 @@ struct frt_ctx {
     DevBuf<unsigned long long> sp_wave_rays{bufs};
     DevBuf<int32_t> sp_pixels{bufs};
     DevBuf<float> sp_rays{bufs};   // frtx_radiance_rays: the host call's device copy of its list
+    // frtx_prt_transfer / frtx_prt_rays (frt_prt.hip): the corner records, the directions with
+    // their Y table, the chunk partials of one batch of corners, the previous and the current
+    // bounce, the per-wave ray counters, the host calls' device copies of T and of the outputs;
+    // for the rays their records and hits and the device triangle of every scene-view triangle
+    DevBuf<float4> prt_corner{bufs}, prt_rays{bufs}, prt_hits{bufs};
+    DevBuf<float> prt_albedo{bufs}, prt_dirs{bufs}, prt_y{bufs}, prt_partial{bufs}, prt_bounce_a{bufs}, prt_bounce_b{bufs};
+    DevBuf<float> prt_t{bufs}, prt_rgb{bufs};
+    DevBuf<unsigned long long> prt_wave_rays{bufs};
+    DevBuf<int32_t> prt_inv{bufs};
 };
 
 #pragma GCC visibility push(hidden)

@@ -8,9 +8,11 @@
 
 #include "frt_ctx.hpp"
 #include "frt_flatten.hpp"
+#include "frt_prt.hpp"
 #include "frt_rays.hpp"
 #include "frt_tree_passes.hpp"
 #include "host/envdist.hpp"
+#include "host/prt.hpp"
 
 using namespace frt;
 
@@ -407,6 +409,140 @@ extern "C" int frtx_selftest_trace_host(const frt_scene_view *sv, const float *r
         r[0] = h.t; r[1] = h.u; r[2] = h.v;
         const float refbits = i2f(ref);
         memcpy(&r[3], &refbits, sizeof(float));
+    }
+    return FRT_OK;
+}
+
+// ---- precomputed radiance transfer on the host (frt.h): frt_prt.hpp, the code the
+// kernels of frt_prt.hip run per lane, over the host traversal of frtx_selftest_trace_host ----
+
+// one ray of a corner, as frt_trace_device answers its record
+static Hit<float> prt_trace_host(const DevScene &S, f3 o, f3 d, bool anyhit, int *stack)
+{
+    return S.world_kind == FRT_WORLD_LIST ? trace<FRT_WORLD_LIST, 1>(S, o, d, kPrtTmax, anyhit, stack)
+                                          : trace<FRT_WORLD_BVH, 1>(S, o, d, kPrtTmax, anyhit, stack);
+}
+
+// one bounce over every corner, batched and reduced as transfer_impl (frt_prt.hip) does
+template <bool GATHER>
+static void prt_bounce_host(const DevScene &S, std::vector<int> &stack, const std::vector<float> &on, const std::vector<float> &rho,
+                            const float *dirs, const std::vector<float> &Y, int n_dirs, bool unshadowed, size_t budget,
+                            const float *Tprev, float *Tcur, float *Tout)
+{
+    constexpr int NACC = GATHER ? kPrtT : kPrtCoef;
+    const size_t nc = rho.size() / 3;
+    const int n_chunks = (n_dirs + kPrtChunk - 1) / kPrtChunk;
+    const float scale = 4.0f / (float)n_dirs;
+    const size_t nb_max = prt_batch_corners(budget, n_chunks, NACC, nc);
+    std::vector<float> partial;
+    for (size_t c0 = 0; c0 < nc; c0 += nb_max) {
+        const size_t nb = std::min(nb_max, nc - c0);
+        partial.assign((size_t)n_chunks * nb * NACC, 0.0f);
+        for (size_t ci = 0; ci < nb; ++ci) {
+            const float *q = &on[8 * (c0 + ci)];
+            const f3 o = mk3(q[0], q[1], q[2]), n = mk3(q[4], q[5], q[6]);
+            for (int chunk = 0; chunk < n_chunks; ++chunk) {
+                float acc[NACC] = {};
+                const int j0 = chunk * kPrtChunk, jn = std::min(kPrtChunk, n_dirs - j0);
+                for (int j = j0; j < j0 + jn; ++j) {
+                    const f3 d = mk3(dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
+                    const float cj = prt_cos(n, d);
+                    if (!(cj > 0.0f)) continue;
+                    if constexpr (!GATHER) {
+                        if (unshadowed || prt_trace_host(S, o, d, true, stack.data()).prim < 0) prt_add(acc, cj, &Y[(size_t)kPrtCoef * j]);
+                    } else {
+                        const Hit<float> h = prt_trace_host(S, o, d, false, stack.data());
+                        if (h.prim >= 0 && !(h.prim & FRT_PRIM_SPHERE)) {
+                            float u, v;
+                            prt_bary(S, h.prim, o, d, u, v);
+                            if (prt_front(S, h.prim, o, d, u, v))
+                                prt_gather(acc, cj, u, v, Tprev + (size_t)S.tri_view[h.prim] * (3 * kPrtT));
+                        }
+                    }
+                }
+                memcpy(&partial[((size_t)chunk * nb + ci) * NACC], acc, sizeof(acc));
+            }
+        }
+        for (size_t ci = 0; ci < nb; ++ci)
+            for (int k = 0; k < kPrtCoef; ++k)
+                for (int ch = 0; ch < 3; ++ch) {
+                    const size_t at = (c0 + ci) * kPrtT + 3 * k + ch;
+                    const float *p = GATHER ? &partial[ci * kPrtT + 3 * k + ch] : &partial[ci * kPrtCoef + k];
+                    const float v = prt_final(rho[3 * (c0 + ci) + ch], scale, prt_chunk_sum(p, n_chunks, nb * NACC));
+                    if (Tcur) Tcur[at] = v;
+                    Tout[at] = GATHER ? Tout[at] + v : v;
+                }
+    }
+}
+
+// frtx_prt_transfer on the host: the request refused as the entry point refuses it (the text in
+// frt_last_error(NULL)), then the corners, the Y table and the bounces, in the entry point's batches
+// (frt_prt::batch_budget; frtx_selftest_prt_budget sets it for both).
+extern "C" int frtx_selftest_prt_transfer_host(const frt_scene_view *sv, const float *dirs, int64_t n_dirs, int bounces, int flags,
+                                               float *T)
+{
+    auto fail = [](int code, const std::string &m) { frt::null_ctx_err() = m; return code; };
+    if (!sv) return fail(FRT_E_INVALID, "prt_transfer: bad arguments");
+    const std::string refused = frt_prt::transfer_request_bad(dirs, n_dirs, bounces, flags);   // the entry point's validator
+    if (!refused.empty()) return fail(FRT_E_INVALID, refused);
+    if (sv->n_tris == 0) return FRT_OK;
+    if (!T) return fail(FRT_E_INVALID, "prt_transfer: bad arguments");
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false);
+    if (rc != FRT_OK) return fail(rc, err);
+    const DevScene S = host_scene(F);
+    const size_t nc = (size_t)sv->n_tris * 3;
+    std::vector<float> on(nc * 8), rho(nc * 3), Y((size_t)n_dirs * kPrtCoef);
+    const std::string bad = frt_prt::corners(sv, on.data(), rho.data());
+    if (!bad.empty()) return fail(FRT_E_INVALID, bad);
+    frt_prt::y_table(dirs, n_dirs, Y.data());
+    const size_t budget = frt_prt::batch_budget();
+    std::vector<int> stack(std::max(F.depth + 1, 1));
+    std::vector<float> a(bounces > 0 ? nc * kPrtT : 0), b(a.size()), out(nc * kPrtT);
+    float *cur = bounces > 0 ? a.data() : nullptr, *prev = b.data();
+    for (int k = 0; k <= bounces; ++k) {
+        if (k == 0) prt_bounce_host<false>(S, stack, on, rho, dirs, Y, (int)n_dirs, (flags & FRTX_PRT_UNSHADOWED) != 0, budget, prev, cur, out.data());
+        else prt_bounce_host<true>(S, stack, on, rho, dirs, Y, (int)n_dirs, false, budget, prev, cur, out.data());
+        std::swap(cur, prev);
+    }
+    memcpy(T, out.data(), out.size() * sizeof(float));
+    return FRT_OK;
+}
+
+// frtx_prt_rays on the host: the closest hit of every ray as frtx_selftest_trace_host takes it,
+// then prt_shade; env: an environment image or NULL (the view's constant colour)
+extern "C" int frtx_selftest_prt_rays_host(const frt_scene_view *sv, const frt_image *env, const float *T, const float *li,
+                                           const float *rays, int64_t n, float *rgb)
+{
+    auto fail = [](int code, const std::string &m) { frt::null_ctx_err() = m; return code; };
+    if (!sv || !li || n < 0 || (n > 0 && (!rays || !rgb)) || (sv->n_tris > 0 && !T)) return fail(FRT_E_INVALID, "prt_rays: bad arguments");
+    for (int k = 0; k < kPrtT; ++k)
+        if (!std::isfinite(li[k])) return fail(FRT_E_INVALID, "prt_rays: li[" + std::to_string(k) + "] is not finite");
+    std::string why;
+    if (frt::rays_first_bad(rays, n, why) >= 0) return fail(FRT_E_INVALID, "prt_rays: " + why);
+    FlatScene F;
+    std::string err;
+    const int rc = flatten_scene(sv, F, err, false);
+    if (rc != FRT_OK) return fail(rc, err);
+    DevScene S = host_scene(F);
+    std::vector<float4> env_tex;
+    if (env) {
+        const int erc = env_texels_of(env, env_tex, err);
+        if (erc != FRT_OK) return fail(erc, err);
+        S.env_texels = env_tex.data(); S.env_nx = env->nx; S.env_ny = env->ny;
+    }
+    std::vector<int> inv(std::max(sv->n_tris, 1), 0);
+    for (int d = 0; d < sv->n_tris; ++d) inv[F.tri_view[d]] = d;
+    std::vector<int> stack(std::max(F.depth + 1, 1));
+    for (int64_t i = 0; i < n; ++i) {
+        const float *q = rays + 8 * i;
+        const f3 o = mk3(q[0], q[1], q[2]), d = mk3(q[4], q[5], q[6]);
+        const Hit<float> h = S.world_kind == FRT_WORLD_LIST ? trace<FRT_WORLD_LIST, 1>(S, o, d, q[3], false, stack.data())
+                                                            : trace<FRT_WORLD_BVH, 1>(S, o, d, q[3], false, stack.data());
+        const int ref = (h.prim < 0 || (h.prim & FRT_PRIM_SPHERE)) ? h.prim : F.tri_view[h.prim];
+        const f3 c = prt_shade(S, inv.data(), T, li, o, d, make_float4(h.t, h.u, h.v, i2f(ref)));
+        rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
     }
     return FRT_OK;
 }

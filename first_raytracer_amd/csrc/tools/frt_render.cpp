@@ -3,7 +3,8 @@
 // compile-time choices.  Writes the linear film as PFM (image.h:89-118).
 //
 //   frt_render --scene cornell|veach|obj --obj FILE [--res 1920x1080] [--ns 512]
-//              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals|albedo|depth] [--chains 262144]
+//              [--seed 0] [--gpus 1] [--integrator path|pssmlt|ao|normals|albedo|depth|prt] [--chains 262144]
+//              [--prt-dirs 32] [--prt-bounces 1] [--prt-unshadowed]
 //              [--denoise [--denoise-spp 16]]
 //              [--error-out v.pfm] [--target-error E --max-spp N [--first-spp 16] [--adaptive [--switch S]]]
 //              [--env r,g,b | --env-map file.hdr [--env-sampling]] [--roulette] [--sobol] [--out out.pfm] [--png out.png] [--bvh reference|sah]
@@ -13,6 +14,11 @@
 // --integrator ao / normals: renderer<ao_gpu> / renderer<normals_gpu> (ao.h, debug_renderer.h).
 // --integrator albedo / depth: the first-hit feature images (FRT_INTEGRATOR_ALBEDO / _DEPTH, frt.h):
 //   reflectance colour; (depth x coverage, its second moment, coverage).
+// --integrator prt: precomputed radiance transfer (frt.h) in one run on the first GPU: the
+//   transfer of the scene over --prt-dirs^2 stratified directions (seeded by --seed) with --prt-bounces
+//   interreflections (--prt-unshadowed: bounce 0 without visibility rays), the projection of the
+//   environment (--env-map, or the constant --env / the scene's colour), then the frame through the
+//   scene's camera with --ns samples a pixel; prints the precompute's kernel ms and rays.
 // --denoise: after the last pass of a path or pssmlt render, filter the film (FRT_INTEGRATOR_DENOISE:
 //   an a-trous wavelet filter guided by --denoise-spp samples of normals, albedo and depth, on the
 //   first GPU) before --out / --png are written; prints the feature and filter times.
@@ -75,6 +81,8 @@ int main(int argc, char **argv)
     int cam_passes = 1;
     double cam_origin[3] = {0, 0, 0};
     bool has_cam_origin = false;
+    int prt_dirs = 32, prt_bounces = 1;
+    bool prt_unshadowed = false, has_prt_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -115,6 +123,9 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%lf,%lf,%lf", &cam_origin[0], &cam_origin[1], &cam_origin[2]) != 3) return 2;
             has_cam_origin = true;
         }
+        else if (a == "--prt-dirs") { prt_dirs = std::atoi(next()); has_prt_flag = true; }
+        else if (a == "--prt-bounces") { prt_bounces = std::atoi(next()); has_prt_flag = true; }
+        else if (a == "--prt-unshadowed") { prt_unshadowed = has_prt_flag = true; }
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "--obj is required\n"); return 2; }
@@ -134,6 +145,13 @@ int main(int argc, char **argv)
     }
     if (denoise && integrator != "path" && integrator != "pssmlt") {
         std::fprintf(stderr, "--denoise: only a path or pssmlt film is filtered\n");
+        return 2;
+    }
+    if (has_prt_flag && integrator != "prt") { std::fprintf(stderr, "--prt-dirs / --prt-bounces / --prt-unshadowed go with --integrator prt\n"); return 2; }
+    if (integrator == "prt" && (prt_dirs < 1 || prt_dirs > 4096 || prt_bounces < 0 || prt_bounces > 16 || ns < 1 || gpus != 1 || denoise ||
+                                !camera.empty())) {
+        std::fprintf(stderr, "--integrator prt: --prt-dirs in [1, 4096], --prt-bounces in [0, 16], --ns >= 1, one GPU, "
+                             "not with --denoise or --camera\n");
         return 2;
     }
     const bool until = has_target;
@@ -254,6 +272,22 @@ int main(int argc, char **argv)
             film.store_film(up.data());
             std::printf("Lat-long probe from (%g, %g, %g): %d passes of %ld samples, %llu rays, %.3f ms on the GPU\n", cam_origin[0],
                         cam_origin[1], cam_origin[2], cam_passes, ns, rays, ms);
+        } else if (integrator == "prt") {   // precompute + projection + render, on the first GPU
+            frt::renderer<frt::path_gpu> render;
+            render.seed = seed;
+            const frt_render_params p = render.params(nx, ny, (int)ns);
+            const frt_scene_view view = s.view();
+            frt::device_set gpu({0}, view, s.env_map());
+            std::vector<float> T;
+            const frt_stats pre = frt::prt_transfer(gpu.data()[0], view, frt::prt_sample_dirs(prt_dirs, seed), prt_bounces,
+                                                    prt_unshadowed ? FRTX_PRT_UNSHADOWED : 0, T);
+            std::printf("PRT precompute: %d directions, %d bounces, %llu rays, %.3f ms on the GPU\n", prt_dirs * prt_dirs, prt_bounces,
+                        (unsigned long long)(pre.shadow_rays + pre.extension_rays), pre.kernel_ms);
+            const std::vector<double> li = frt::sh_project(s.env_map(), view.env_color);
+            std::vector<float> rgb((size_t)nx * ny * 3);
+            const frt_stats st = frt::prt_render(gpu.data()[0], p, T, li, rgb.data());
+            film.store_film(rgb.data());
+            std::printf("PRT render: %llu rays, %.3f ms on the GPU\n", (unsigned long long)st.camera_rays, st.kernel_ms);
         } else if (integrator == "pssmlt") {
             frt::renderer<frt::pssmlt_gpu> render;
             render.chains = chains;

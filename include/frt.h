@@ -767,6 +767,99 @@ int frtx_selftest_radiance_host(const frt_scene_view *scene, const frt_render_pa
 int frtx_selftest_camera_rays_host(const frt_scene_view *scene, const frt_render_params *p, const int32_t *pixels,
                                    int64_t npix, float *rays_out);
 
+/* ---- precomputed radiance transfer (the reference's path_prt integrator, path_prt.cpp, prt.h;
+ *      DESIGN.md 5f).  Diffuse PRT after Sloan et al. 2002: a scene is baked once into per-corner
+ *      transfer vectors and can then be relit under any environment at the cost of one first-hit
+ *      query and a 25-term dot product per ray.  Not the reference's arithmetic: its frames are
+ *      inconsistent and its interreflection estimator converges to nothing meaningful (DESIGN.md 5f
+ *      lists the deviations).
+ * Basis: 5 bands, 25 real SH coefficients, index k = l (l + 1) + m, K and P with the Condon-Shortley
+ *   phase as prt.h EstimateSH has them.  One convention throughout, frt_set_env_image's: for a unit
+ *   direction d, theta = acos(d.y), phi = atan2(d.x, -d.z) (+ 2 pi when negative), Y_k(d) =
+ *   EstimateSH(l, m, theta, phi).
+ * Corner records: one per (triangle t of the scene view, corner i), index 3 t + i, in fp64 rounded to
+ *   fp32.  Normal n: tri_n where the view has vertex normals and tri_geometry_normal[t] is 0, else
+ *   the normalised e1 x e2.  Origin o = v + 1e-4 n.  Albedo rho: a lambertian triangle's texture at
+ *   the corner's uv (constant, checker or image, by the kernels' index rules in fp64); 0 for every
+ *   other material.  Spheres have no corners, they only occlude.
+ * Directions: n_dirs unit vectors, 3 floats each.  Nothing is normalised; a direction that is not
+ *   finite or whose length is off 1 by more than 1e-3 is FRT_E_INVALID with its index in the text.
+ *   Y_k of every direction is taken in fp64 and rounded to fp32 once (frtx_prt_basis gives that table).
+ * Transfer T[3 t + i][k][ch], n_tris x 3 x 25 x 3 floats, = sum over bounces b = 0 .. B of T^b:
+ *   T^0[c][k][ch] = rho[c][ch] (4 / n_dirs) sum_j [cos_j > 0 and ray j unoccluded] cos_j Y_k(d_j),
+ *     cos_j = dot(n_c, d_j) in fp32, ray j = (o_c, d_j, t_max = FLT_MAX) answered as frt_trace_device
+ *     answers that record with the any-hit flag; FRTX_PRT_UNSHADOWED traces nothing;
+ *   T^b, b >= 1: the same directions with a closest-hit query; a ray that hits triangle q at (u, v)
+ *     on its front side (dot(q's shading normal at the hit, -d) > 0) gathers (1 - u - v) T^(b-1)[q, 0]
+ *     + u T^(b-1)[q, 1] + v T^(b-1)[q, 2], weighted rho[c][ch] (4 / n_dirs) cos_j; a miss, a sphere
+ *     or a back side gathers 0.
+ *   Order of the sums (part of the contract): the directions are cut into chunks of 64; a corner's
+ *   terms of a chunk are added in ascending j into fp32 accumulators, the chunk sums in ascending
+ *   chunk order, rho and 4 / n_dirs (fp32) are applied last as (rho * scale) * sum.  The result does
+ *   not depend on how the work was scheduled or batched.
+ * Environment Li[k][ch] (frtx_sh_project_image, fp64): sum over texels of value Y_k(theta_y, phi_x)
+ *   sin(theta_y) (2 pi / nx) (pi / ny), theta_y = pi (y + 1/2) / ny, phi_x = 2 pi (x + 1/2) / nx, row
+ *   0 at the +y pole, value = the fp32 texel image_texture's lookup returns.  img = NULL: the
+ *   constant colour, Li[0] = E sqrt(4 pi), the rest 0.
+ * Vertices at junctions: a corner's transfer is taken at the vertex itself.  A vertex that lies in the
+ *   plane of a neighbouring wall (every vertex of the Cornell box) starts half of its rays in that
+ *   plane and misses it, so it sees the environment through the junction, and gathers carry that light
+ *   on (the reference's vertices do the same).  On such meshes PRT is brighter near junctions than the
+ *   path integrator; the two agree on scenes without junctions (tests/test_prt_host.py).
+ * Shading a ray (frtx_prt_rays): the closest hit comes from frt_trace_device.  On a lambertian
+ *   triangle rgb[ch] = sum_k (ascending) Li[k][ch] interp(T[q, .][k][ch]); on a diffuse_light its
+ *   emit (shown, but PRT lighting is the environment only); on any other material or a sphere 0; on
+ *   a miss the context's environment in the ray's direction as every integrator looks it up. */
+#define FRTX_PRT_UNSHADOWED (1 << 16)   /* frtx_prt_transfer flags: bounce 0 without visibility rays */
+/* host only: Y[n][25] of n directions (checked as above) */
+int frtx_prt_basis(const float *dirs, int64_t n, float *Y);
+/* host only: li[25][3] of an image (frt_set_env_image's formats and refusals) or of env_color */
+int frtx_sh_project_image(const frt_image *img_or_null, const double env_color[3], double li[75]);
+/* host only: sqrt_n^2 jittered strata, uniform on the sphere, jitter from the counter hash keyed by
+ * (seed, stratum), in the convention above; dirs = sqrt_n^2 x 3 floats; sqrt_n in [1, 4096] */
+int frtx_prt_sample_dirs(int sqrt_n, uint32_t seed, float *dirs);
+/* host only: the corner records; origin_normal = n_tris x 3 x 8 floats (o, 0, n, 0), albedo x 3 */
+int frtx_prt_corners(const frt_scene_view *scene, float *origin_normal, float *albedo);
+/* The transfer of the uploaded scene.  `scene` is the view that was uploaded: the corner records
+ * are taken from its fp64 arrays, of which an upload keeps none (a view with another triangle
+ * count is FRT_E_INVALID; one with the same count and other vertices bakes that view's corners
+ * against the uploaded scene: passing the uploaded view is the caller's part of the contract).  flags: FRTX_PRT_UNSHADOWED, and FRT_FLAG_BVH2 to select the binary tree
+ * (_NO_LDS_SCENE and _NO_OCT do nothing: the kernels read the scene from HBM).  T is written only
+ * when the call succeeds; n_tris = 0 returns FRT_OK and writes nothing.  FRT_E_NO_SCENE before an
+ * upload; FRT_E_INVALID with a text for n_dirs < 1, bounces outside [0, 16], a bad direction, unknown
+ * flags.  st: kernel_ms (transfer and reduce kernels), shadow_rays = the visibility rays of bounce 0,
+ * extension_rays = the gather rays, work_items, and the plan as frt_trace_device fills it.
+ * frtx_prt_transfer: T in host memory.  frtx_prt_transfer_device: T in device memory, the work on
+ * hip_stream (NULL: the context's); returns when it is done.  dirs is host memory in both. */
+int frtx_prt_transfer(frt_ctx *ctx, const frt_scene_view *scene, const float *dirs, int64_t n_dirs, int bounces, int flags,
+                      float *T, frt_stats *st);
+int frtx_prt_transfer_device(frt_ctx *ctx, const frt_scene_view *scene, const float *dirs, int64_t n_dirs, int bounces, int flags,
+                             float *T, void *hip_stream, frt_stats *st);
+/* rgb[3 i ..] of ray i (frt_trace_device's record, checked as frtx_radiance_rays checks it; word 7
+ * is not read).  li = 75 floats in host memory.  st: camera_rays = n, kernel_ms (the ray query and
+ * the shade kernel), the ray query's plan.  frtx_prt_rays: T, rays and rgb in host memory;
+ * frtx_prt_rays_device: in device memory, on hip_stream (NULL: the context's). */
+int frtx_prt_rays(frt_ctx *ctx, const float *T, const float *li, const float *rays, int64_t n, float *rgb, frt_stats *st);
+int frtx_prt_rays_device(frt_ctx *ctx, const float *T, const float *li, const float *rays, int64_t n, float *rgb,
+                         void *hip_stream, frt_stats *st);
+/* A PRT frame through the scene's own camera: film = nx x ny x 3 floats in host memory (index
+ * (y nx + x) 3, y = 0 the bottom row, as frt_render's).  Per sample s of p->spp the first rays a
+ * render makes for every pixel at sample p->sample_offset + s (frtx_camera_rays_device: seed,
+ * FRT_FLAG_SOBOL) are shaded as frtx_prt_rays shades them, and the samples are averaged by
+ * frt_film_accumulate's rule.  T and li in host memory.  st: camera_rays = samples = nx ny spp,
+ * kernel_ms over the samples, the ray query's plan. */
+int frtx_prt_render(frt_ctx *ctx, const frt_render_params *p, const float *T, const float *li, float *film, frt_stats *st);
+/* Test hook: the bytes of chunk sums one batch of corners may take in frtx_prt_transfer and in its
+ * replay (0: the default, 256 MiB).  The result of a transfer never depends on it. */
+int frtx_selftest_prt_budget(int64_t bytes);
+/* The two calls through the same code on the host (csrc/frt_prt.hpp over the host traversal of
+ * frtx_selftest_trace_host), refusing what they refuse with the text in frt_last_error(NULL);
+ * env: an environment image or NULL (the view's env_color). */
+int frtx_selftest_prt_transfer_host(const frt_scene_view *scene, const float *dirs, int64_t n_dirs, int bounces, int flags,
+                                    float *T);
+int frtx_selftest_prt_rays_host(const frt_scene_view *scene, const frt_image *env, const float *T, const float *li,
+                                const float *rays, int64_t n, float *rgb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -435,6 +435,52 @@ inline std::vector<float> latlong_rays(const double origin[3], int nx, int ny, d
     return rays;
 }
 
+// Precomputed radiance transfer (frt.h "precomputed radiance transfer"; the reference's path_prt).
+// sh_project: li[25][3] of an environment image, or (img NULL) of a constant colour.
+inline std::vector<double> sh_project(const frt_image *img, const double env_color[3] = nullptr)
+{
+    std::vector<double> li(75);
+    check(frtx_sh_project_image(img, env_color, li.data()), "frtx_sh_project_image");
+    return li;
+}
+// sqrt_n^2 stratified unit directions (3 floats each) for prt_transfer
+inline std::vector<float> prt_sample_dirs(int sqrt_n, uint32_t seed = 0)
+{
+    std::vector<float> dirs((size_t)(sqrt_n > 0 ? sqrt_n : 1) * (size_t)(sqrt_n > 0 ? sqrt_n : 1) * 3);
+    check(frtx_prt_sample_dirs(sqrt_n, seed, dirs.data()), "frtx_prt_sample_dirs");
+    return dirs;
+}
+// frtx_prt_transfer on one context: T[n_tris][3][25][3] of the uploaded scene, whose view is passed again
+inline frt_stats prt_transfer(frt_ctx *ctx, const frt_scene_view &scene, const std::vector<float> &dirs, int bounces, int flags,
+                              std::vector<float> &T)
+{
+    T.assign((size_t)scene.n_tris * 3 * 75, 0.0f);
+    frt_stats st{};
+    check(frtx_prt_transfer(ctx, &scene, dirs.data(), (int64_t)(dirs.size() / 3), bounces, flags, T.data(), &st), "frtx_prt_transfer", ctx);
+    return st;
+}
+// frtx_prt_rays on one context: rgb (n x 3 floats) of n ray records (host memory) under li (sh_project)
+inline frt_stats prt_rays(frt_ctx *ctx, const std::vector<float> &T, const std::vector<double> &li, const float *rays, int64_t n,
+                          float *rgb)
+{
+    float l[75];
+    for (int k = 0; k < 75; ++k) l[k] = (float)li.at((size_t)k);
+    frt_stats st{};
+    check(frtx_prt_rays(ctx, T.data(), l, rays, n, rgb, &st), "frtx_prt_rays", ctx);
+    return st;
+}
+
+// frtx_prt_render on one context: the nx x ny frame of `p` through the scene's camera, p.spp samples
+inline frt_stats prt_render(frt_ctx *ctx, const frt_render_params &p, const std::vector<float> &T, const std::vector<double> &li,
+                            float *film)
+{
+    float l[75];
+    for (int k = 0; k < 75; ++k) l[k] = (float)li.at((size_t)k);
+    frt_stats st{};
+    check(frtx_prt_render(ctx, &p, T.data(), l, film, &st), "frtx_prt_render", ctx);
+    return st;
+}
+
 // The active share of the frame below which an adaptive pass goes through frtx_render_pixels: the
 // full render's time over the sparse kernel's for the same pixels and samples, rounded down to one
 // decimal (1080p, 64 spp, one MI355X: profiles/adaptive/switch.json).  The binding's ADAPTIVE_SWITCH.
